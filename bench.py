@@ -19,6 +19,13 @@ distinct input/output buffers (>= --rotate-gb) that the 256 MB Infinity Cache
 cannot serve repeated launches.  Timing: HIP events on the launch stream
 around exactly --steps steps, barrier + synchronize on both sides, max over
 ranks.  Rank 0 prints one JSON line.
+
+A plain run does only that: set up, settle, warm up, time --steps steps, print.
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds every other measurement after the headline run: the kernel-only
+pass and the roofline priced from it, the variants (other configs, the training
+steps, the calibrator fit), the CPU baseline and, with a collective, the
+per-batch all-reduce leg (--no-variants / --no-cpu-baseline trim it).
 """
 import argparse
 import ctypes
@@ -225,6 +232,7 @@ class Runner:
             self.step()
             if collective:
                 collective()
+        self.last_step = self.i - 1  # drain() realigns the counter: keep the last batch's index
         if collective:
             collective.drain()  # every batch's all-reduce completes inside the timed region
         e1.record(self.stream)
@@ -234,6 +242,37 @@ class Runner:
             dist.barrier()
         torch.cuda.synchronize(self.dev)
         return e0.elapsed_time(e1) / 1e3, wall
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: every array together
+
+
+def dump_outputs(runner, out_dir):
+    """Write what the last timed step (Runner.timed's last_step) computed -- the
+    arrays a caller of that pass receives: the final z [B, D], the per-sample
+    log-det [B] and, for the loss pass, the batch's (loss, ce, ld) sums [3] --
+    as out_dir/<name>.npy, float32.  Outputs larger than DUMP_MAX_BYTES are cut
+    to a fixed, seeded sample of rows (the same rows of z and log-det, in
+    ascending order).  Call it right after timed(), before any later step
+    overwrites the rotating buffers.  Returns a description for the result line."""
+    torch.cuda.synchronize(runner.dev)
+    B, D = runner.w["B"], runner.w["D"]
+    k = runner.last_step % runner.nsets  # its inputs: synthetic_logits(B, D, dev, 1234 + k)
+    _, _, out, ld, _ = runner.sets[k]
+    rows = min(B, (DUMP_MAX_BYTES - 1024) // (4 * (D + 1)))  # 1 KB: the sums, the .npy headers
+    if rows < B:
+        pick = np.sort(np.random.RandomState(0).choice(B, rows, replace=False))
+        pick = torch.from_numpy(pick).to(runner.dev)
+        out, ld = out[pick], ld[pick]
+    arrays = {"z": out, "log_det": ld}
+    if runner.mode == "loss":
+        arrays["nll_sums"] = runner.terms
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32))
+    return {"arrays": {k: list(v.shape) for k, v in arrays.items()}, "rows": rows, "of": B,
+            "step": runner.last_step, "input_set": k}
 
 
 NLL_BUCKET = 50  # batches per NLL all-reduce (bench.py --nll-bucket)
@@ -496,6 +535,40 @@ def self_launch(n, argv):
     return rc
 
 
+def kernel_roofline(runner, args, w, mode, world, dev):
+    """--full: the kernel-only pass of the headline runner (runs of its own) and
+    the roofline priced from it; returns (roofline, every rank's kernel us)."""
+    # dominant kernel: average device time per launch, no collective in between
+    k_avg = kernel_only_seconds(runner, max(50, args.steps // 2))
+    # each rank's own kernel-only time beside its step time: on N > 1 the
+    # difference is the NLL all-reduce, the spread across ranks is kernel spread
+    rank_kernel_us = [round(k_avg * 1e6, 3)]
+    if world > 1:
+        kt = torch.tensor([k_avg], dtype=torch.float64, device=dev)
+        every_k = [torch.zeros_like(kt) for _ in range(world)]
+        dist.all_gather(every_k, kt)
+        rank_kernel_us = [round(v.item() * 1e6, 3) for v in every_k]
+    bytes_vec = algo_bytes_per_vec(w["D"], w["L"], labels=(mode == "loss"))
+    flops_vec = algo_flops_per_vec(w["D"], w["L"], w["hidden"], w["scale"])
+    mfma_bound = w["D"] >= 32
+    roof = roofline(w["B"], bytes_vec, flops_vec, k_avg, mfma=mfma_bound)
+    roof.update({
+        "traffic": None,
+        "kernel": runner.stack.kernel_name(),
+        "kernel_avg_us": round(k_avg * 1e6, 3),
+        "timed_kernels": ("%s + k_reduce_rows4 (block-order NLL sum): the whole cnf_forward_loss "
+                          "call, HIP events on its stream" % runner.kernel_symbol()) if mode == "loss"
+                         else runner.kernel_symbol(),
+        "algo_bytes_per_vec": bytes_vec, "algo_flops_per_vec": flops_vec,
+        "rotating_sets": runner.nsets,
+    })
+    tr = measured_traffic(args.workload, w["B"], mode)
+    if tr is not None:
+        roof["traffic"] = tr["traffic_bytes_per_launch"]
+        roof["traffic_source"] = tr["source"]
+    return roof, rank_kernel_us
+
+
 def main():
     global NLL_BUCKET
     ap = argparse.ArgumentParser()
@@ -507,8 +580,15 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="vectors per GPU (default: config)")
     ap.add_argument("--rotate-gb", type=float, default=1.0)
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure everything else: the kernel-only "
+                         "pass and its roofline, the variants, the CPU baseline and, with a "
+                         "collective, the per-batch all-reduce leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the variants")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--overlap-allreduce", action="store_true",
                     help="run each NLL bucket's all-reduce under the next bucket's kernels")
@@ -563,7 +643,13 @@ def main():
         collective = NllAllReduce(runner, overlap=args.overlap_allreduce)
 
     settle_steps = runner.settle(args.settle_s) if args.settle_s > 0 else 0
+    # settle() runs for a time, not a count: restart the rotation so the warmup
+    # and the timed steps meet the same input sets in every run
+    runner.i = 0
     t_dev, wall = runner.timed(args.steps, args.warmup, collective)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(runner, args.dump_outputs)
     sync_ms = None
     if args.dist_check:
         last = runner.terms.clone()
@@ -572,9 +658,9 @@ def main():
         sync_ms = round(ts / args.steps * 1e3, 5)
     # SURVEY 8(e) as written: one NLL all-reduce per batch.  The bucketed run
     # above is the headline; the literal form is timed beside it on the same
-    # ranks, so the first multi-GPU run answers both.
+    # ranks, so the first multi-GPU run with --full answers both.
     literal = None
-    if collective and NLL_BUCKET != 1:
+    if args.full and collective and NLL_BUCKET != 1:
         keep = NLL_BUCKET
         NLL_BUCKET = 1
         t_lit, _ = runner.timed(args.steps, args.warmup,
@@ -603,37 +689,12 @@ def main():
     total_vecs = w["B"] * world * args.steps
     value = total_vecs / t_max
 
-    # dominant kernel: average device time per launch, no collective in between
-    k_avg = kernel_only_seconds(runner, max(50, args.steps // 2))
-    # each rank's own kernel-only time beside its step time: on N > 1 the
-    # difference is the NLL all-reduce, the spread across ranks is kernel spread
-    rank_kernel_us = [round(k_avg * 1e6, 3)]
-    if world > 1:
-        kt = torch.tensor([k_avg], dtype=torch.float64, device=dev)
-        every_k = [torch.zeros_like(kt) for _ in range(world)]
-        dist.all_gather(every_k, kt)
-        rank_kernel_us = [round(v.item() * 1e6, 3) for v in every_k]
-    bytes_vec = algo_bytes_per_vec(w["D"], w["L"], labels=(mode == "loss"))
-    flops_vec = algo_flops_per_vec(w["D"], w["L"], w["hidden"], w["scale"])
-    mfma_bound = w["D"] >= 32
-    roof = roofline(w["B"], bytes_vec, flops_vec, k_avg, mfma=mfma_bound)
-    roof.update({
-        "traffic": None,
-        "kernel": runner.stack.kernel_name(),
-        "kernel_avg_us": round(k_avg * 1e6, 3),
-        "timed_kernels": ("%s + k_reduce_rows4 (block-order NLL sum): the whole cnf_forward_loss "
-                          "call, HIP events on its stream" % runner.kernel_symbol()) if mode == "loss"
-                         else runner.kernel_symbol(),
-        "algo_bytes_per_vec": bytes_vec, "algo_flops_per_vec": flops_vec,
-        "rotating_sets": runner.nsets,
-    })
-    tr = measured_traffic(args.workload, w["B"], mode)
-    if tr is not None:
-        roof["traffic"] = tr["traffic_bytes_per_launch"]
-        roof["traffic_source"] = tr["source"]
+    roof, rank_kernel_us = None, None
+    if args.full:
+        roof, rank_kernel_us = kernel_roofline(runner, args, w, mode, world, dev)
 
     variants = {}
-    if rank == 0 and world == 1 and not args.no_variants:
+    if args.full and rank == 0 and world == 1 and not args.no_variants:
         for name, wl, allo in (("cfg2_forward_ld", WORKLOADS["cfg2"], False),
                                ("cfg2_all_zs", WORKLOADS["cfg2"], True),
                                ("cfg5_inverse", WORKLOADS["cfg5"], False),
@@ -655,7 +716,7 @@ def main():
         variants["calibrator_fit_epoch"] = calibrator_epoch_rate(dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, args.cpu_seconds)
 
     if rank == 0:
@@ -672,8 +733,6 @@ def main():
             # ms/step (ms_per_step above is their max)
             "ranks": dist.get_world_size() if dist.is_initialized() else 1,
             "rank_ms_per_step": rank_ms,
-            # each rank's kernel-only time per launch (no collective in between)
-            "rank_kernel_us": rank_kernel_us,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s: %d-layer %s coupling, D=%d, hidden_size=%s, %d vectors "
@@ -684,15 +743,20 @@ def main():
                        "global_batch": w["B"] * world, "parallelism": "dp%d" % world,
                        "hidden_size": w["hidden"], "weights": ("N(0,%g) synthetic" % w.get("sigma", 0.1)) if w.get("sigma", 0.1) is not None
                        else "the reference's default Linear init (synthetic)"},
-            "roofline": roof,
         "step": "fused forward + log-det + NLL sums (cnf_forward_loss)%s" % (
             " + RCCL all-reduce of every batch's NLL sums, %d batches per all-reduce%s" % (
                 NLL_BUCKET, " (overlapping the next bucket)" if args.overlap_allreduce else "")
             if collective else "") if mode == "loss"
             else "fused pass (cnf_%s)" % ("inverse" if w["inverse"] else "forward"),
-            "cpu_baseline": cpu,
             "wall_s": round(wall, 4),
         }
+        if args.full:
+            # each rank's kernel-only time per launch (no collective in between)
+            out["rank_kernel_us"] = rank_kernel_us
+            out["roofline"] = roof
+            out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if variants:
             out["variants"] = variants
         if literal is not None:

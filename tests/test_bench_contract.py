@@ -166,3 +166,51 @@ def test_nll_all_reduce_realigns_after_uncollected_batches(monkeypatch):
                 expect.extend(range(first, r.i))
                 coll.drain()
             assert sorted(reduced) == expect, (pre, warm, steps)
+
+
+def test_dump_outputs_writes_the_last_step_and_caps_its_size(monkeypatch, tmp_path):
+    """bench.dump_outputs (--dump-outputs): the last timed step's buffers as
+    float32 .npy files; past the size cap a fixed, seeded, ascending row sample,
+    the same rows of z and log-det, identical from call to call."""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda dev=None: None)
+    B, D, nsets = 50, 9, 3
+
+    class FakeRunner:
+        dev = torch.device("cpu")
+        w = {"B": B, "D": D}
+        mode = "loss"
+
+        def __init__(self):
+            self.nsets = nsets
+            self.sets = [(None, None, torch.randn(B, D) + k, torch.randn(B) + k, None)
+                         for k in range(nsets)]
+            self.terms = torch.tensor([3.0, 2.0, -1.0])
+            self.last_step = 7  # set 7 % 3 = 1
+
+    r = FakeRunner()
+    info = bench.dump_outputs(r, str(tmp_path / "all"))
+    z = np.load(tmp_path / "all" / "z.npy")
+    ld = np.load(tmp_path / "all" / "log_det.npy")
+    sums = np.load(tmp_path / "all" / "nll_sums.npy")
+    assert z.dtype == ld.dtype == sums.dtype == np.float32
+    assert info["rows"] == B and info["step"] == 7
+    assert np.array_equal(z, r.sets[1][2].numpy()) and np.array_equal(ld, r.sets[1][3].numpy())
+    assert sums.tolist() == [3.0, 2.0, -1.0]
+
+    cap = 2000
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", cap)
+    rows = (cap - 1024) // (4 * (D + 1))
+    assert 0 < rows < B
+    for name in ("s1", "s2"):
+        info = bench.dump_outputs(r, str(tmp_path / name))
+        assert info["rows"] == rows and info["of"] == B
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= cap
+    z1, z2 = np.load(tmp_path / "s1" / "z.npy"), np.load(tmp_path / "s2" / "z.npy")
+    l1 = np.load(tmp_path / "s1" / "log_det.npy")
+    assert z1.shape == (rows, D) and l1.shape == (rows,) and np.array_equal(z1, z2)
+    # the sample is rows of the full output, ascending, the same for z and log-det
+    idx = [int(np.flatnonzero((z == row).all(axis=1))[0]) for row in z1]
+    assert idx == sorted(set(idx)) and np.array_equal(l1, ld[idx])

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 : > gpurun_out/dist_check.jsonl
 for b in ${@:-50 1}; do
-  timeout -k 10 200 python bench.py --dist-check --no-variants --no-cpu-baseline --nll-bucket $b \
+  timeout -k 10 200 python bench.py --full --dist-check --no-variants --no-cpu-baseline --nll-bucket $b \
     > gpurun_out/dist_check_$b.log 2>&1 || { tail -5 gpurun_out/dist_check_$b.log; exit 1; }
   python - "$b" << 'PY'
 import json, sys

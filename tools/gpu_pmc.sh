@@ -4,7 +4,7 @@
 set -u
 TAG=$1; WL=$2; EXTRA=$3; shift 3
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-OUT=gpurun_out/pmc_${TAG}_${WL}
+OUT=${CNF_RECORD_DIR:-session_out}/pmc_${TAG}_${WL}
 mkdir -p $OUT
 export TMPDIR=/tmp
 i=0

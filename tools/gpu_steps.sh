@@ -5,7 +5,7 @@
 # Usage: bash tools/gpu_steps.sh step [step ...]
 #   tests        pytest -m gpu (whole GPU suite)
 #   smoke        __graft_entry__.smoke()
-#   bench        python bench.py (default line)
+#   bench        python bench.py --full (headline, roofline, variants, CPU baseline)
 #   trace        k_sgpr per-wave timeline (libcnf_hip_trace.so), loss + forward
 #   rate         tools/quick_rate.py loss / forward (2^20 and 2^23 rows)
 #   ab           tools/quick_rate.py $AB_MODE for every tools/ab/lib*.so (make ab)
@@ -41,7 +41,7 @@ for step in "$@"; do
   case "$step" in
     tests) TAILN=12 CNF_RECORD_DIR=gpurun_out run tests 600 python -u -m pytest tests -m gpu -q -rfs --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) TAILN=2 run bench 600 python bench.py ;;
+    bench) TAILN=2 run bench 600 python bench.py --full ;;
     trace) CNF_TRACE_DUMP=gpurun_out/trace_loss.npz run trace_loss 180 python tools/sgpr_trace.py loss && CNF_TRACE_DUMP=gpurun_out/trace_fwd.npz run trace_fwd 180 python tools/sgpr_trace.py forward ;;
     rate) run rate 300 python tools/quick_rate.py loss forward inverse ;;
     train) run train 300 python -c "import json, torch, bench; d = torch.device('cuda:0'); print(json.dumps({w: bench.train_step_rate(d, w, steps=(20 if w == 'cfg2' else 5)) for w in ('cfg2', 'cfg4')}))" ;;
