@@ -57,6 +57,17 @@ class Calibrator:
         probs = self.predict_post(logits)
         return softmax(np.log(probs + 1e-7) - self.log_priors, axis=1)
 
+    def evaluate(self, logits, target, bins=15):
+        """Score the calibrated predictions of `logits` against `target`
+        (labels or one-hot rows): {"nll", "ece", "accuracy", "n"} as
+        utils.metrics computes them on predict()'s float64 probabilities."""
+        from utils import metrics as M
+        probs = self.predict(logits)
+        target = np.asarray(target)
+        return {"nll": M.neg_log_likelihood(probs, target),
+                "ece": M.expected_calibration_error(probs, target, bins=bins),
+                "accuracy": M.accuracy(probs, target), "n": int(probs.shape[0])}
+
 
 class DummyCalibrator(Calibrator):
     """Uncalibrated model (calibrators.py:47-53)."""
@@ -310,24 +321,52 @@ class TorchFlowCalibrator(Calibrator):
             self._replica = (key, rep)
         return self._replica[1]
 
+    def _predict_device(self, logits):
+        """predict()'s fp32 probabilities as a tensor on self.dev, or None when
+        no native stack serves this flow there (then predict() runs on the host)."""
+        if torch.device(self.dev).type != "cuda":
+            return None
+        flow = self._device_flow()
+        stack = _native_stack(flow, self.dev, need_vjp=False)
+        if stack is None:
+            return None
+        x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
+        if self._lp_dev is None:
+            self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float, device=self.dev)
+        with torch.no_grad():
+            return stack.predict(x, self._lp_dev)
+
     def predict(self, logits):
         """Calibrator.predict (calibrators.py:40-44 with predict_post, :330-353):
         centring, the flow, softmax and the prior correction
         softmax(log(p + 1e-7) - log_priors).  On a ROCm device this is ONE fused
         launch (cnf_predict) on a resident replica of the flow, with one H2D
         copy of the logits and one D2H copy of the probabilities."""
-        if torch.device(self.dev).type == "cuda":
-            flow = self._device_flow()
-            stack = _native_stack(flow, self.dev, need_vjp=False)
-            if stack is not None:
-                x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
-                if self._lp_dev is None:
-                    self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float,
-                                                   device=self.dev)
-                with torch.no_grad():
-                    probs = stack.predict(x, self._lp_dev)
-                return probs.cpu().numpy().astype(np.float64)
+        probs = self._predict_device(logits)
+        if probs is not None:
+            return probs.cpu().numpy().astype(np.float64)
         return super().predict(logits)
+
+    def evaluate_sums(self, logits, target, bins=15, record=None):
+        """The calibration record of predict(logits) against `target` (labels
+        or one-hot rows) as cnf_hip.metrics.CalibrationSums.  On a ROCm device
+        the probabilities stay there: the resident replica's fused predict,
+        one cnf_metrics launch, and ONE D2H copy of the 4 + 3 * bins record
+        words instead of the B * D probabilities.  `record` (int64 tensor on
+        the scoring device) accumulates over calls."""
+        from cnf_hip.metrics import CalibrationSums, calibration_record
+        target = np.asarray(target)
+        if target.ndim == 2:
+            target = np.argmax(target, axis=1)
+        probs = self._predict_device(logits)
+        if probs is None:
+            probs = torch.as_tensor(super().predict(logits))
+        y = torch.as_tensor(target.astype(np.int64)).to(probs.device)
+        return CalibrationSums(calibration_record(probs, y, bins, record), bins)
+
+    def evaluate(self, logits, target, bins=15):
+        """{"nll", "ece", "accuracy", "n"} of predict(logits), from evaluate_sums."""
+        return self.evaluate_sums(logits, target, bins).as_dict()
 
     def predict_logits(self, logits):
         logits = torch.as_tensor(logits, dtype=torch.float)

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("CNF_HIP_LIB", os.path.join(_HERE, "libcnf_hip.so"))
 ABI_VERSION = 2
 MAX_HIDDEN = 8
 MAX_DIM = 256
+MAX_BINS = 64     # CNF_MAX_BINS (cnf_metrics)
 LOSS_CAL = 0
 LOSS_CE = 1
 OPT_NO_SGPR = 1   # cnf_desc.options (include/cnf.h)
@@ -32,6 +33,7 @@ EXPORTS = (
     "cnf_predict", "cnf_vjp_workspace_bytes", "cnf_vjp", "cnf_loss_vjp", "cnf_adam_step",
     "cnf_adam_step_sched", "cnf_adam_step_guarded",
     "cnf_vjp_inverse_workspace_bytes", "cnf_vjp_inverse", "cnf_guard_nonfinite",
+    "cnf_metrics_record_words", "cnf_metrics_workspace_bytes", "cnf_metrics",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -99,6 +101,10 @@ def _bind(lib):
         "cnf_adam_step_guarded": (ctypes.c_int, [D, ctypes.POINTER(P), P, P, P, I64, DB, P, DB,
                                                  DB, DB, DB, P, P]),
         "cnf_guard_nonfinite": (ctypes.c_int, [P, I64, P, P]),
+        "cnf_metrics_record_words": (ctypes.c_int, [I32, ctypes.POINTER(I64)]),
+        "cnf_metrics_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_metrics": (ctypes.c_int, [P, P, I32, I32, I64, P, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),

@@ -214,6 +214,21 @@ def sharded_nll(flow, x, y, group=None, kind=_lib.LOSS_CAL, det=1.0):
     return terms
 
 
+@torch.no_grad()
+def sharded_calibration_record(probs, y, bins=15, group=None):
+    """The calibration record (cnf_hip.metrics) of ALL shards: this rank's
+    rows through calibration_record (one cnf_metrics launch on a ROCm device,
+    the torch restatement on CPU), then ONE all-reduce (SUM) of the
+    4 + 3 * bins int64 words.  ECE is not a mean of per-row terms, so it cannot
+    ride with the three loss sums above; the per-bin integer sums can, and the
+    reduced record equals the single-process record word for word."""
+    from .metrics import calibration_record
+    record = calibration_record(probs, y, bins)
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(record, group=group)
+    return record
+
+
 def shard(n, rank, world):
     """Contiguous [start, stop) of rank's shard of n rows."""
     per = (n + world - 1) // world

@@ -20,6 +20,9 @@
 //   cnf::vjp_inverse(z, prepared, desc, perms, gx, gx_all, gld, need_dz) -> (grads, dz)
 //   cnf::predict(x, prepared, desc, perms, log_priors) -> probs
 //       Calibrator.predict                     calibrators.py:40-44, 330-353
+//   cnf::metrics(probs, y, bins, record) -> ()
+//       adds the calibration record (NLL / ECE / accuracy sums) of a device
+//       probability matrix into `record`        utils/metrics.py:6-15, 35-80
 //
 // `desc` is the descriptor as integers: [dim, n_layers, n_hidden, hidden[0..7],
 // scale, shift, strict_nan, options]; `perms` an optional host int64 [L, D]
@@ -226,6 +229,25 @@ Tensor predict_impl(const Tensor& x_, const Tensor& prepared, c10::IntArrayRef d
   return probs;
 }
 
+void metrics_impl(const Tensor& probs_, const Tensor& y_, int64_t bins, Tensor record) {
+  DevGuard guard(probs_.device());
+  TORCH_CHECK(probs_.is_cuda() && probs_.scalar_type() == torch::kFloat32 && probs_.dim() == 2,
+              "cnf::metrics: probs must be a ROCm fp32 [B, D] tensor");
+  TORCH_CHECK(bins >= 1 && bins <= CNF_MAX_BINS, "cnf::metrics: bins must be 1..", CNF_MAX_BINS);
+  TORCH_CHECK(record.is_cuda() && record.device() == probs_.device() &&
+                  record.scalar_type() == torch::kInt64 && record.is_contiguous() &&
+                  record.numel() == 4 + 3 * bins,
+              "cnf::metrics: record must be a contiguous int64 [", 4 + 3 * bins,
+              "] tensor on the device of probs");
+  Tensor probs = probs_.contiguous();
+  Tensor y = y_.to(probs.device(), torch::kInt64).contiguous();
+  TORCH_CHECK(y.dim() == 1 && y.size(0) == probs.size(0), "cnf::metrics: y must be [B] labels");
+  check("cnf_metrics",
+        cnf_metrics(probs.data_ptr<float>(), y.data_ptr<int64_t>(), (int32_t)probs.size(1),
+                    (int32_t)bins, probs.size(0), record.data_ptr<int64_t>(), nullptr, 0,
+                    stream(probs)));
+}
+
 // Autograd: forward = one fused launch, backward = cnf_vjp (recomputes the
 // forward inside; nothing but x is saved).  INV: the inverse transform
 // (Flow.backward), backward = cnf_vjp_inverse.
@@ -317,6 +339,7 @@ TORCH_LIBRARY(cnf, m) {
         "Tensor[] params) -> (Tensor, Tensor)");
   m.def("vjp_inverse(Tensor z, Tensor prepared, int[] desc, Tensor? perms, Tensor? gx, "
         "Tensor? gx_all, Tensor? gld, bool need_dz) -> (Tensor, Tensor)");
+  m.def("metrics(Tensor probs, Tensor y, int bins, Tensor(a!) record) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
@@ -328,6 +351,7 @@ TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
   m.impl("loss_and_grads", loss_and_grads_impl);
   m.impl("vjp", vjp_impl);
   m.impl("predict", predict_impl);
+  m.impl("metrics", metrics_impl);
 }
 
 TORCH_LIBRARY_IMPL(cnf, Autograd, m) {

@@ -44,9 +44,9 @@ typedef enum cnf_status {
   CNF_ERR_NULL = -1,          /* a required pointer is NULL                   */
   CNF_ERR_DESC = -2,          /* malformed descriptor (dims, abi_version)     */
   CNF_ERR_UNSUPPORTED = -3,   /* shape outside every kernel's envelope        */
-  CNF_ERR_BATCH = -4,         /* negative batch                               */
+  CNF_ERR_BATCH = -4,         /* negative batch, or above cnf_metrics' row limit */
   CNF_ERR_HIP = -5,           /* a HIP launch/copy failed (cnf_last_hip_error) */
-  CNF_ERR_ALIGN = -6          /* pointer not 4-byte aligned                   */
+  CNF_ERR_ALIGN = -6          /* pointer not aligned to its element (4 or 8 bytes) */
 } cnf_status;
 
 /* The shape of one Flow made of NvpCouplingLayers (flows/flows.py:68-99). */
@@ -236,6 +236,38 @@ int cnf_adam_step_guarded(const cnf_desc* desc, float* const* params, const floa
  * zeroed flag can accumulate over many launches and be read once.  One
  * HBM-bound pass; an atomic OR only from a wave that found something. */
 int cnf_guard_nonfinite(const float* data, int64_t n, int32_t* flag, void* stream);
+
+/* On-device calibration scoring of a probability matrix (the reference's
+ * utils/metrics.py:6-15, 35-80: neg_log_likelihood, expected_calibration_error,
+ * accuracy), e.g. of cnf_predict's output, without copying it to the host:
+ *   probs  [B][D]  fp32 probabilities, 2 <= D <= CNF_MAX_DIM
+ *   y      [B]     int64 labels
+ *   bins           1..CNF_MAX_BINS equal-width confidence bins (reference: 15)
+ * Per row the prediction is the FIRST index of the row maximum (np.argmax),
+ * the confidence is that maximum, and bin i holds the row iff
+ * i*width < conf <= (i+1)*width, conf widened to double, width = 1.0/bins in
+ * double (a confidence <= 0 or > 1 falls in no bin).  The NLL term is
+ * -log(p[y] + 1e-7) on the widened p[y].  A row whose label is outside
+ * [0, D), that holds a non-finite entry, or whose p[y] + 1e-7 is not positive
+ * (no finite term) counts in n_invalid and in nothing else. */
+#define CNF_MAX_BINS 64
+/* record: int64 words
+ *   [0] n_rows   [1] n_invalid   [2] nll_fx   [3] n_correct
+ *   [4 .. 4+bins)          rows per bin
+ *   [4+bins .. 4+2*bins)   conf_fx per bin
+ *   [4+2*bins .. 4+3*bins) correct rows per bin
+ * *_fx: sums of rint(value * 2^32), value widened to double first
+ * n_rows counts the valid rows.  Every word is an integer sum, so a record is
+ * bitwise repeatable and independent of grid, batch split and shard split;
+ * records of shards add word by word.  cnf_metrics ADDS into `record`: the
+ * caller zeroes it once (as with cnf_guard_nonfinite's flag), so one record
+ * can cover many batches or graph replays.  A term is < 2^5, so one record
+ * holds 2^26 rows; B > 2^26 is CNF_ERR_BATCH.  The workspace size is 0 (blocks
+ * add with integer atomics; workspace may be NULL). */
+int cnf_metrics_record_words(int32_t bins, int64_t* words);
+int cnf_metrics_workspace_bytes(int32_t dim, int32_t bins, int64_t B, size_t* bytes);
+int cnf_metrics(const float* probs, const int64_t* y, int32_t dim, int32_t bins, int64_t B,
+                int64_t* record, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,

@@ -104,6 +104,44 @@ int main(int argc, char** argv) {
     EXPECT(cnf_adam_step(&d, nullptr, dummy, dummy, dummy, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0,
                          nullptr) <= 0);
     EXPECT(cnf_guard_nonfinite(dummy, -1, nullptr, nullptr) < 0);
+    // calibration scoring: size queries with random shapes, then the launching
+    // entry point with one rejected argument each (range, batch, NULL, alignment)
+    {
+      const int32_t mdim = U(0, 4) == 0 ? U(-3, 400) : U(2, CNF_MAX_DIM);
+      const int32_t mbins = U(0, 4) == 0 ? U(-3, 90) : U(1, CNF_MAX_BINS);
+      const bool shape_ok = mdim >= 2 && mdim <= CNF_MAX_DIM && mbins >= 1 && mbins <= CNF_MAX_BINS;
+      int64_t words = -1;
+      size_t mws = 1;
+      const int sw = cnf_metrics_record_words(mbins, &words);
+      EXPECT(is_status(sw));
+      EXPECT((sw == CNF_OK) == (mbins >= 1 && mbins <= CNF_MAX_BINS));
+      if (sw == CNF_OK) EXPECT(words == 4 + 3 * (int64_t)mbins);
+      const int sb = cnf_metrics_workspace_bytes(mdim, mbins, B, &mws);
+      EXPECT(is_status(sb));
+      EXPECT((sb == CNF_OK) == (shape_ok && B >= 0));
+      if (sb == CNF_OK) EXPECT(mws == 0);
+      EXPECT(cnf_metrics_workspace_bytes(mdim, mbins, B, nullptr) == CNF_ERR_NULL);
+      alignas(8) int64_t lab[2] = {0, 0};
+      alignas(8) int64_t rec[4 + 3 * CNF_MAX_BINS] = {0};
+      const int sm = cnf_metrics(dummy, lab, mdim, mbins, nb, rec, nullptr, 0, nullptr);
+      EXPECT(sm < 0 && is_status(sm));
+      if (shape_ok) {
+        EXPECT(sm == CNF_ERR_BATCH);
+        EXPECT(cnf_metrics(dummy, lab, mdim, mbins, (1LL << 26) + 1, rec, nullptr, 0, nullptr) ==
+               CNF_ERR_BATCH);
+        EXPECT(cnf_metrics(nullptr, lab, mdim, mbins, 1, rec, nullptr, 0, nullptr) == CNF_ERR_NULL);
+        EXPECT(cnf_metrics(dummy, nullptr, mdim, mbins, 1, rec, nullptr, 0, nullptr) == CNF_ERR_NULL);
+        EXPECT(cnf_metrics(dummy, lab, mdim, mbins, 1, nullptr, nullptr, 0, nullptr) == CNF_ERR_NULL);
+        EXPECT(cnf_metrics((const float*)((const char*)dummy + 2), lab, mdim, mbins, 1, rec, nullptr,
+                           0, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_metrics(dummy, (const int64_t*)((const char*)lab + 4), mdim, mbins, 1, rec,
+                           nullptr, 0, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_metrics(dummy, lab, mdim, mbins, 1, (int64_t*)((char*)rec + 4), nullptr, 0,
+                           nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_metrics(nullptr, nullptr, mdim, mbins, 0, rec, nullptr, 0, nullptr) == CNF_OK);
+        for (int64_t w : rec) EXPECT(w == 0);  // nothing was written
+      }
+    }
     delete perms;
   }
   EXPECT(cnf_param_count(nullptr, nullptr) == CNF_ERR_NULL);
