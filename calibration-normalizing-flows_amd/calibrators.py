@@ -10,8 +10,17 @@ ONE fused forward + loss launch (cnf_forward_loss); history entries stay
 device tensors, as in the reference, so no step synchronises the host.
 Any other flow (or a CPU device) runs the reference's own torch loop.
 
-Out of scope here (host-side, non-flow calibrators of the reference):
-TempScaling / Matrix / Vector / MLR / PAV calibrators (calibrators.py:55-236).
+The scaling baselines -- TempScalingCalibrator, MLRCalibrator,
+VectorScalingCalibrator, MatrixScalingCalibrator (calibrators.py:57-205) --
+keep the reference's constructor `(logits, target)`, attributes and SciPy
+calls.  NumPy inputs fit in float64 on the host; a ROCm fp32 tensor `logits`
+(labels or one-hot rows as a tensor or array) stays on the device, where every
+objective / gradient evaluation is one cnf_scaling_loss_grad call
+(cnf_hip/scaling.py), and `predict` of a ROCm tensor is one
+cnf_scaling_predict launch that returns a ROCm fp32 tensor.
+
+Out of scope here: PAVCalibrator (sklearn isotonic regression on the host,
+calibrators.py:208-236) and TempScaler.
 """
 import numpy as np
 import torch
@@ -74,6 +83,188 @@ class DummyCalibrator(Calibrator):
 
     def predict_post(self, logits):
         return softmax(logits, axis=1)
+
+
+class _ScalingCalibrator(Calibrator):
+    """Shared by the four scaling calibrators: the host / device convention
+    (module docstring), and `fun` / `jac` formed from the raw sums
+    [loss | gb | ga] of utils.ops.scaling_sums_fn exactly as the reference
+    forms them."""
+
+    kind = None
+
+    def __init__(self, logits, target):
+        from utils import ops
+        if ops._is_device(logits):
+            labels = ops.hard_labels(target, logits.shape)
+            if labels is None or logits.dtype != torch.float32:  # soft targets: host path
+                logits = logits.detach().cpu().numpy().astype(np.float64)
+                target = target.detach().cpu().numpy() if torch.is_tensor(target) else target
+        if ops._is_device(logits):
+            # centred once, in float64, and rounded back to the fp32 the kernels read
+            x = logits.detach().double()
+            self.logits = (x - x.mean(dim=1, keepdim=True)).float()
+            self.n_classes = int(logits.shape[1])
+            if labels.size and (labels.min() < 0 or labels.max() >= self.n_classes):
+                raise ValueError("labels must lie in [0, %d)" % self.n_classes)
+            self.target = torch.from_numpy(labels).to(logits.device)
+            priors = np.bincount(labels, minlength=self.n_classes).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                self.log_priors = np.log(priors / np.sum(priors))
+        else:
+            super().__init__(np.asarray(logits), np.asarray(target))
+        self._setup()
+        self.fit(self.logits, self.target)
+
+    def _setup(self):
+        pass
+
+    def _map(self):
+        """(a, b) of the fitted map t = A(x) + b, as cnf_scaling_predict takes them."""
+        raise NotImplementedError
+
+    def predict(self, logits):
+        from utils import ops
+        if ops._is_device(logits):
+            from cnf_hip import scaling
+            a, b = self._map()
+            return scaling.predict(logits, self.kind, a, b, self.log_priors)
+        if torch.is_tensor(logits):
+            logits = logits.detach().numpy()
+        return super().predict(np.asarray(logits, dtype=np.float64))
+
+
+class TempScalingCalibrator(_ScalingCalibrator):
+    """softmax(logits / T), T from utils.ops.optim_temperature's Newton-CG run
+    (calibrators.py:57-68).  Quirk kept: the objective carries the 1e-7, the
+    gradient -mean(sum((p - t) * x)) / T^2 does not."""
+
+    kind = 0
+
+    def fit(self, logits, target):
+        from utils import ops
+        self.T, self.optim = ops._optim_temperature(logits, target)
+
+    def _map(self):
+        return [1. / self.T], None
+
+    def predict_post(self, logits):
+        return softmax(logits / self.T, axis=1)
+
+
+class MatrixScalingCalibrator(_ScalingCalibrator):
+    """softmax(logits @ W + b), SciPy CG from zeros (calibrators.py:71-116).
+    Quirk kept: the objective evaluates logits @ (W + b), b broadcast over W's
+    rows, while the gradient is that of logits @ W + b, so the line search
+    usually ends with "precision loss", as the reference's does."""
+
+    kind = 2
+
+    def _setup(self):
+        self.n = self.n_classes
+        self.W = np.zeros([self.n, self.n])
+        self.b = np.zeros(self.n)
+
+    def fit(self, logits, target):
+        from scipy.optimize import minimize
+        from utils import ops
+        n = self.n
+        sums, B, _ = ops.scaling_sums_fn(logits, target, self.kind)
+        zero = np.zeros(n)
+
+        def fun(x):
+            return sums((x[n:].reshape(n, n) + x[:n]).ravel(), zero, False)[0] / B
+
+        def jac(x):
+            s = sums(x[n:], x[:n], True)
+            return np.concatenate([s[1:1 + n], s[1 + n:]]) / B
+
+        self._fun, self._jac = fun, jac
+        x0 = np.concatenate((self.b, self.W.ravel()))
+        self.optim = minimize(fun, x0=x0, method='CG', jac=jac)
+        self.b = self.optim.x[:n]
+        self.W = self.optim.x[n:].reshape([n, n])
+
+    def _map(self):
+        return self.W.ravel(), self.b
+
+    def predict_post(self, logits):
+        return softmax(logits @ self.W + self.b, axis=1)
+
+
+class VectorScalingCalibrator(_ScalingCalibrator):
+    """softmax(W * logits + b), SciPy CG from zeros (calibrators.py:119-161).
+    Quirk kept: the bias gradient is the one scalar mean(p - t) over all
+    elements, broadcast to every class, so b never leaves rounding noise."""
+
+    kind = 1
+
+    def _setup(self):
+        self.n = self.n_classes
+        self.W = np.zeros(self.n)
+        self.b = np.zeros(self.n)
+
+    def fit(self, logits, target):
+        from scipy.optimize import minimize
+        from utils import ops
+        n = self.n
+        sums, B, _ = ops.scaling_sums_fn(logits, target, self.kind)
+
+        def fun(x):
+            return sums(x[n:], x[:n], True)[0] / B
+
+        def jac(x):
+            s = sums(x[n:], x[:n], True)
+            grad = np.zeros(x.shape)
+            grad[:n] = np.sum(s[1:1 + n]) / (B * n)
+            grad[n:] = s[1 + n:] / B
+            return grad
+
+        self._fun, self._jac = fun, jac
+        x0 = np.concatenate((self.b, self.W))
+        self.optim = minimize(fun, x0=x0, method='CG', jac=jac)
+        self.b = self.optim.x[:n]
+        self.W = self.optim.x[n:]
+
+    def _map(self):
+        return self.W, self.b
+
+    def predict_post(self, logits):
+        return softmax(self.W * logits + self.b, axis=1)
+
+
+class MLRCalibrator(_ScalingCalibrator):
+    """softmax(alpha * logits + gamma), SciPy CG from (1, 0) (calibrators.py:164-205)."""
+
+    kind = 0
+
+    def _setup(self):
+        self.alpha = 1.
+        self.gamma = np.zeros(self.n_classes)
+
+    def fit(self, logits, target):
+        from scipy.optimize import minimize
+        from utils import ops
+        sums, B, D = ops.scaling_sums_fn(logits, target, self.kind)
+
+        def fun(x):
+            return sums(x[:1], x[1:], True)[0] / B
+
+        def jac(x):
+            s = sums(x[:1], x[1:], True)
+            return np.concatenate([s[1 + D:], s[1:1 + D]]) / B
+
+        self._fun, self._jac = fun, jac
+        x0 = np.concatenate(([self.alpha], self.gamma))
+        self.optim = minimize(fun, x0=x0, method='CG', jac=jac)
+        self.alpha = self.optim.x[0]
+        self.gamma = self.optim.x[1:]
+
+    def _map(self):
+        return [self.alpha], self.gamma
+
+    def predict_post(self, logits):
+        return softmax(self.alpha * logits + self.gamma, axis=1)
 
 
 def _native_stack(flow, dev, need_vjp=True):

@@ -25,6 +25,10 @@ OPT_NO_SGPR = 1   # cnf_desc.options (include/cnf.h)
 OPT_NO_WIDE = 2
 OPT_ALT_MASK = 4  # legacy code-old/realNVP.py semantics (flows/legacy.py)
 OPT_S_TANH = 8
+SCALE_SCALAR = 0  # CNF_SCALE_* (cnf_scaling_*): t = a*x + b, a one double
+SCALE_DIAG = 1    # t = w.x + b
+SCALE_FULL = 2    # t = x@W + b, D <= SCALE_FULL_MAX_DIM
+SCALE_FULL_MAX_DIM = 128
 
 # Every symbol include/cnf.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -34,6 +38,8 @@ EXPORTS = (
     "cnf_adam_step_sched", "cnf_adam_step_guarded",
     "cnf_vjp_inverse_workspace_bytes", "cnf_vjp_inverse", "cnf_guard_nonfinite",
     "cnf_metrics_record_words", "cnf_metrics_workspace_bytes", "cnf_metrics",
+    "cnf_scaling_sums_words", "cnf_scaling_workspace_bytes", "cnf_scaling_loss_grad",
+    "cnf_scaling_predict",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -105,6 +111,12 @@ def _bind(lib):
         "cnf_metrics_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
                                                        ctypes.POINTER(ctypes.c_size_t)]),
         "cnf_metrics": (ctypes.c_int, [P, P, I32, I32, I64, P, P, ctypes.c_size_t, P]),
+        "cnf_scaling_sums_words": (ctypes.c_int, [I32, I32, ctypes.POINTER(I64)]),
+        "cnf_scaling_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_scaling_loss_grad": (ctypes.c_int, [P, P, I32, I32, P, P, I32, I64, P, P,
+                                                 ctypes.c_size_t, P]),
+        "cnf_scaling_predict": (ctypes.c_int, [P, I32, I32, P, P, P, P, I64, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),

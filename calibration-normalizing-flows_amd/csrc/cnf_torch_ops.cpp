@@ -23,6 +23,11 @@
 //   cnf::metrics(probs, y, bins, record) -> ()
 //       adds the calibration record (NLL / ECE / accuracy sums) of a device
 //       probability matrix into `record`        utils/metrics.py:6-15, 35-80
+//   cnf::scaling_loss_grad(x, y, kind, a, b?, want_grad, sums, workspace) -> ()
+//       objective and gradient sums of the temperature / MLR / vector / matrix
+//       scaling fits                            calibrators.py:57-205, utils/ops.py:69-115
+//   cnf::scaling_predict(x, kind, a, b?, log_priors) -> probs
+//       Calibrator.predict of a fitted scaling map   calibrators.py:40-44
 //
 // `desc` is the descriptor as integers: [dim, n_layers, n_hidden, hidden[0..7],
 // scale, shift, strict_nan, options]; `perms` an optional host int64 [L, D]
@@ -248,6 +253,64 @@ void metrics_impl(const Tensor& probs_, const Tensor& y_, int64_t bins, Tensor r
                     stream(probs)));
 }
 
+// a, b, log_priors, sums: float64 tensors on x's device (cnf_scaling_*)
+const double* dptr(const Tensor& t, const Tensor& x, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() && t.scalar_type() == torch::kFloat64 &&
+                  t.is_contiguous() && t.numel() == n,
+              "cnf::scaling: ", what, " must be a contiguous float64 tensor of ", n,
+              " elements on the device of x");
+  return t.data_ptr<double>();
+}
+
+int64_t scaling_a_len(int64_t kind, int64_t D) {
+  return kind == CNF_SCALE_SCALAR ? 1 : kind == CNF_SCALE_DIAG ? D : D * D;
+}
+
+void scaling_loss_grad_impl(const Tensor& x_, const Tensor& y_, int64_t kind, const Tensor& a,
+                            const c10::optional<Tensor>& b, bool want_grad, Tensor sums,
+                            Tensor workspace) {
+  DevGuard guard(x_.device());
+  TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == torch::kFloat32 && x_.dim() == 2,
+              "cnf::scaling_loss_grad: x must be a ROCm fp32 [B, D] tensor");
+  Tensor x = x_.contiguous();
+  Tensor y = y_.to(x.device(), torch::kInt64).contiguous();
+  const int64_t B = x.size(0), D = x.size(1);
+  TORCH_CHECK(y.dim() == 1 && y.size(0) == B, "cnf::scaling_loss_grad: y must be [B] labels");
+  int64_t words = 0;
+  check("cnf_scaling_sums_words", cnf_scaling_sums_words((int32_t)kind, (int32_t)D, &words));
+  const double* pa = dptr(a, x, scaling_a_len(kind, D), "a");
+  const bool has_b = b.has_value() && b->defined();
+  const double* pb = has_b ? dptr(*b, x, D, "b") : nullptr;
+  TORCH_CHECK(sums.numel() >= (want_grad ? words : 1), "cnf::scaling_loss_grad: sums too short");
+  dptr(sums, x, sums.numel(), "sums");
+  TORCH_CHECK(workspace.is_cuda() && workspace.device() == x.device() && workspace.is_contiguous(),
+              "cnf::scaling_loss_grad: workspace must be a contiguous tensor on the device of x");
+  check("cnf_scaling_loss_grad",
+        cnf_scaling_loss_grad(x.data_ptr<float>(), y.data_ptr<int64_t>(), (int32_t)kind, (int32_t)D,
+                              pa, pb, want_grad ? 1 : 0, B, sums.data_ptr<double>(),
+                              workspace.data_ptr(), (size_t)workspace.nbytes(), stream(x)));
+}
+
+Tensor scaling_predict_impl(const Tensor& x_, int64_t kind, const Tensor& a,
+                            const c10::optional<Tensor>& b, const Tensor& log_priors) {
+  DevGuard guard(x_.device());
+  TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == torch::kFloat32 && x_.dim() == 2,
+              "cnf::scaling_predict: x must be a ROCm fp32 [B, D] tensor");
+  Tensor x = x_.contiguous();
+  const int64_t B = x.size(0), D = x.size(1);
+  int64_t words = 0;
+  check("cnf_scaling_sums_words", cnf_scaling_sums_words((int32_t)kind, (int32_t)D, &words));
+  const double* pa = dptr(a, x, scaling_a_len(kind, D), "a");
+  const bool has_b = b.has_value() && b->defined();
+  const double* pb = has_b ? dptr(*b, x, D, "b") : nullptr;
+  const double* lp = dptr(log_priors, x, D, "log_priors");
+  Tensor probs = torch::empty_like(x);
+  check("cnf_scaling_predict", cnf_scaling_predict(x.data_ptr<float>(), (int32_t)kind, (int32_t)D,
+                                                   pa, pb, lp, probs.data_ptr<float>(), B,
+                                                   stream(x)));
+  return probs;
+}
+
 // Autograd: forward = one fused launch, backward = cnf_vjp (recomputes the
 // forward inside; nothing but x is saved).  INV: the inverse transform
 // (Flow.backward), backward = cnf_vjp_inverse.
@@ -340,6 +403,9 @@ TORCH_LIBRARY(cnf, m) {
   m.def("vjp_inverse(Tensor z, Tensor prepared, int[] desc, Tensor? perms, Tensor? gx, "
         "Tensor? gx_all, Tensor? gld, bool need_dz) -> (Tensor, Tensor)");
   m.def("metrics(Tensor probs, Tensor y, int bins, Tensor(a!) record) -> ()");
+  m.def("scaling_loss_grad(Tensor x, Tensor y, int kind, Tensor a, Tensor? b, bool want_grad, "
+        "Tensor(a!) sums, Tensor(b!) workspace) -> ()");
+  m.def("scaling_predict(Tensor x, int kind, Tensor a, Tensor? b, Tensor log_priors) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
@@ -352,6 +418,8 @@ TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
   m.impl("vjp", vjp_impl);
   m.impl("predict", predict_impl);
   m.impl("metrics", metrics_impl);
+  m.impl("scaling_loss_grad", scaling_loss_grad_impl);
+  m.impl("scaling_predict", scaling_predict_impl);
 }
 
 TORCH_LIBRARY_IMPL(cnf, Autograd, m) {

@@ -269,6 +269,60 @@ int cnf_metrics_workspace_bytes(int32_t dim, int32_t bins, int64_t B, size_t* by
 int cnf_metrics(const float* probs, const int64_t* y, int32_t dim, int32_t bins, int64_t B,
                 int64_t* record, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Temperature, MLR, vector and matrix scaling on the device: the objective and
+ * gradient sums that the reference's fits hand to SciPy (TempScalingCalibrator,
+ * MatrixScalingCalibrator, VectorScalingCalibrator, MLRCalibrator,
+ * calibrators.py:57-205; optim_temperature, utils/ops.py:69-115) and the
+ * calibrated prediction of the fitted map, for logits resident on the device.
+ * All four minimise mean(-log(softmax(t)[y] + 1e-7)) over an affine map of
+ * the logits:
+ *   CNF_SCALE_SCALAR  t = a*x + b    a: 1 double; b: D doubles or NULL (= 0)
+ *                     (temperature scaling: a = 1/T, no bias; MLR)
+ *   CNF_SCALE_DIAG    t = w.x + b    a = w: D doubles; b: D   (vector scaling)
+ *   CNF_SCALE_FULL    t = x@W + b    a = W: [D][D] row-major, input x output,
+ *                     as the reference's `logits @ W`; b: D   (matrix scaling)
+ * x is fp32 [B][D]; a, b, log_priors and sums are DEVICE float64 arrays.  The
+ * logits are widened on load and everything after that -- the map, the row
+ * maximum, exp, the sum, log, the gradient terms, the sums over rows -- is
+ * float64 (SciPy's Newton-CG differences the gradient below an fp32 ulp of T).
+ * Scalar and diagonal kinds: 2 <= D <= CNF_MAX_DIM; full kind: 2 <= D <= 128
+ * (CNF_ERR_UNSUPPORTED above).  B <= 2^26 (CNF_ERR_BATCH above). */
+#define CNF_SCALE_SCALAR 0
+#define CNF_SCALE_DIAG 1
+#define CNF_SCALE_FULL 2
+
+/* Words of `sums` with want_grad: 1 + D + (1 | D | D*D by kind). */
+int cnf_scaling_sums_words(int32_t kind, int32_t dim, int64_t* words);
+/* Bytes of per-block float64 partial sums a call of B rows writes. */
+int cnf_scaling_workspace_bytes(int32_t kind, int32_t dim, int64_t B, size_t* bytes);
+
+/* One fused pass over (x, y [B] int64 labels).  With p_r = softmax(t_r)
+ * (row maximum subtracted first, as SciPy's softmax) and g_r = p_r - onehot(y_r):
+ *   sums[0]          sum_r -log(p_r[y_r] + 1e-7)
+ * and, when want_grad != 0,
+ *   sums[1 .. 1+D)   sum_r g_rj
+ *   then `ga`:       scalar kind  1 word   sum_r sum_j g_rj x_rj
+ *                    diagonal     D words  sum_r g_rj x_rj
+ *                    full         D*D      ga[i*D + j] = sum_r x_ri g_rj
+ * Raw sums: the caller divides by B and forms the reference's formulas.  With
+ * want_grad == 0 only sums[0] is written.  A label outside [0, D) turns
+ * sums[0] and every gradient word into NaN.  B == 0 zeroes the words and
+ * launches no kernel.  Deterministic: per-block partials in `workspace`, added
+ * in block order by a follow-up launch; the grid depends on (kind, D, B) only,
+ * so two calls agree bitwise.  No float atomics, no allocation, no host sync. */
+int cnf_scaling_loss_grad(const float* x, const int64_t* y, int32_t kind, int32_t dim,
+                          const double* a, const double* b, int32_t want_grad, int64_t B,
+                          double* sums, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fused Calibrator.predict of a scaling map (calibrators.py:40-44 with the
+ * predict_post of :67, :113, :158, :202), per row
+ *   p = softmax(t(x - mean(x))),  probs = softmax(log(p + 1e-7) - log_priors)
+ * computed in float64 and rounded once into fp32 probs [B][D] (ready for
+ * cnf_metrics).  log_priors: D DEVICE doubles.  Same envelope as above. */
+int cnf_scaling_predict(const float* x, int32_t kind, int32_t dim, const double* a,
+                        const double* b, const double* log_priors, float* probs, int64_t B,
+                        void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"
