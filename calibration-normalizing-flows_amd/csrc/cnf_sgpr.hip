@@ -129,6 +129,15 @@ template <int NIN, int NOUT, int S, bool RELU, int P, int NC, class X, class E, 
 __device__ __forceinline__ void slin(const SW<NC>& w, X&& x, E&& emit, F&& before) {
   sready();
   before();
+  if constexpr (NIN == 5 && NOUT == 5 && S == 6 && NC == 2 && P == 1) {
+    // the whole Linear as one asm statement (lin5x5: no hazard nops)
+    const f2 x5[5] = {x(0, 0), x(0, 1), x(0, 2), x(0, 3), x(0, 4)};
+    f2 a5[5];
+    lin5x5<RELU>(w, x5, a5);
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) emit(o, &a5[o]);
+    return;
+  }
   f2 a[NOUT][P];
 #pragma unroll
   for (int o = 0; o < NOUT; ++o)
@@ -291,18 +300,18 @@ __device__ __forceinline__ f2 pair_max(const f2* v) {
 // z[y]: GATHER 1 reads it from the staged output tile (the lane's two rows at
 // tile[0..D) and tile[D..2D): one ds_read_b32 per row instead of a
 // ~30-instruction select tree); GATHER 0 selects from the registers (ragged
-// tile).
+// tile).  idx: the rows' labels, 0 where invalid (ok false): an invalid label
+// reads slot 0 and the NaN goes in with one select on z[y] -- everything
+// downstream of it (ce, loss) is NaN then, and the log-det sum is untouched.
 template <int D, int GATHER>
-__device__ __forceinline__ void pair_loss(const f2* v, f2 ld, uint32_t lab2, int rows, int kind,
-                                          float det, float& t0, float& t1, float& t2,
-                                          const float* tile) {
-  const uint32_t b0 = lab2 & 0xffu, b1 = (lab2 >> 8) & 0xffu;
-  const bool ok[2] = {b0 != 0xffu, b1 != 0xffu};
+__device__ __forceinline__ void pair_loss(const f2* v, f2 ld, const int (&idx)[2],
+                                          const bool (&ok)[2], int rows, int kind, float det,
+                                          float& t0, float& t1, float& t2, const float* tile) {
   constexpr float kL2E = 1.4426950408889634f, kLN2 = 0.6931471805599453f;
   float zy[2];
   if constexpr (GATHER == 1) {  // issued first: the LDS reads overlap the max / sum-exp below
-    zy[0] = tile[ok[0] ? (int)b0 : 0];
-    zy[1] = tile[D + (ok[1] ? (int)b1 : 0)];
+    zy[0] = tile[idx[0]];
+    zy[1] = tile[D + idx[1]];
   }
   const f2 m = pair_max<D>(v);
   const f2 nm = m * splat(-kL2E, f2{});
@@ -316,13 +325,14 @@ __device__ __forceinline__ void pair_loss(const f2* v, f2 ld, uint32_t lab2, int
       za[j] = __float_as_uint(v[j].x);
       zb[j] = __float_as_uint(v[j].y);
     }
-    zy[0] = __uint_as_float(sel_tree<D>(za, ok[0] ? (int)b0 : 0, 0));
-    zy[1] = __uint_as_float(sel_tree<D>(zb, ok[1] ? (int)b1 : 0, 0));
+    zy[0] = __uint_as_float(sel_tree<D>(za, idx[0], 0));
+    zy[1] = __uint_as_float(sel_tree<D>(zb, idx[1], 0));
   }
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     if (q >= rows) continue;
-    const float lpy = zy[q] - (m[q] + __builtin_amdgcn_logf(se[q]) * kLN2);
+    const float zq = ok[q] ? zy[q] : __builtin_nanf("");
+    const float lpy = zq - (m[q] + __builtin_amdgcn_logf(se[q]) * kLN2);
     const float l = ld[q];
     float ce, loss;
     if (kind == CNF_LOSS_CAL) {
@@ -332,7 +342,6 @@ __device__ __forceinline__ void pair_loss(const f2* v, f2 ld, uint32_t lab2, int
       ce = -lpy;
       loss = ce - det * l;
     }
-    if (!ok[q]) ce = loss = __builtin_nanf("");
     t0 += loss;
     t1 += ce;
     t2 += l;
@@ -397,13 +406,36 @@ struct KArgs {
   float* all;             // [L][B][D] every-layer outputs (ALL variants)
   const int64_t* y;       // labels (loss)
   float* part;            // per-block loss partials, 4 floats each (loss)
-  // three unused words: they keep the argument block of the measured build
-  // (the scalar loads of L / kind / det at these offsets; without them the
-  // compiler schedules every variant differently)
-  const void *reserved0, *reserved1, *reserved2;
   int L, kind;
   float det;
 };
+
+// k_sgpr's argument block as the dispatch lays it out (its parameters in
+// order), for the offset of KArgs in it.
+struct KBlock {
+  const float* in;
+  int64_t B;
+  const float *W;
+  const int32_t *qtab, *lflag;
+  const float* lpri;
+  KArgs a;
+};
+typedef const __attribute__((address_space(4))) KBlock* KBlockPtr;
+typedef const __attribute__((address_space(4))) KArgs* KArgsPtr;
+
+// The launch arguments through a pointer the compiler cannot trace back to
+// the argument block: what is read through it is loaded where it is used (one
+// s_load at a tile boundary) and dies there, instead of being loaded once in
+// the prologue and held across the layer loop.  The two SGPR weight buffers
+// take 64 of the 102 SGPRs, and out / ld / y / part / kind / det, the flags
+// derived from them and the LDS-DMA's m0 values, all used only between
+// layer sweeps, were what the allocator rotated through VGPR spill lanes.
+__device__ __forceinline__ KBlockPtr fresh_block() {
+  KBlockPtr p = (KBlockPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+__device__ __forceinline__ KArgsPtr fresh_args() { return &fresh_block()->a; }
 
 // The kernel.  MODE: kFwd / kInv (+ log-det), kLoss (forward + loss terms),
 // kPredict (centre + forward + calibrated probabilities).  ALL: also store
@@ -415,7 +447,9 @@ template <int D, int H1, int H2, int NETS, int MODE, bool ALL, bool PERM>
 // what a wave needs to issue its first tile's LDS-DMA and weight loads; the
 // Makefile builds this file with kernarg preloading of them
 // (-amdgpu-kernarg-preload-count), so they arrive in SGPRs with the wave
-// instead of through dependent s_loads of the argument block.
+// instead of through dependent s_loads of the argument block.  KBlock above
+// mirrors this list: what the tile loop needs only between layer sweeps it
+// reads again from the argument block there (fresh_block / fresh_args).
 __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) void k_sgpr(
     const float* __restrict__ in,       // rows [B][D]
     int64_t B,
@@ -443,12 +477,6 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
     const int m = (int)(reinterpret_cast<uintptr_t>(q) & 15);
     return m == 0 ? 16 : ((m & 7) == 0 ? 8 : 4);
   };
-  // (no longer read: kept because this early look at a.out shapes the
-  // prologue's scalar-load schedule -- without it every variant compiles to a
-  // different instruction stream than the measured build)
-  [[maybe_unused]] const int al = a.out ? align_of(a.out) : 16;
-  const int al_ld = a.ld ? align_of(a.ld) : 16;
-  const bool y16 = MODE == kLoss && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0;
   float lp[MODE == kPredict ? D : 1];
   if constexpr (MODE == kPredict) {
 #pragma unroll
@@ -462,12 +490,18 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
   // below write v[D-1-k] for feature k), so every stack leaves the layer-pair
   // loop in logical order: no unflip, and no register shuffle where the odd
   // and even paths meet (16 v_mov_b64 per tile when the lone layer ran last).
-  const bool odd = (L & 1) != 0;
+  // (tested on an opaque copy of L at each use: as one value the compiler
+  // holds it, and its complement, as 64-bit lane masks across the layer loop)
+  auto is_odd = [&]() {
+    int l = L;
+    asm volatile("" : "+s"(l));
+    return (l & 1) != 0;
+  };
   auto compute = [&](f2 (&v)[P][D], f2 (&ld)[P], int64_t row0, int nr) {
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       if constexpr (MODE == kPredict) {
-        if (odd) centre<D, true>(v[p]);
+        if (is_odd()) centre<D, true>(v[p]);
         else centre<D, false>(v[p]);
       }
       ld[p] = splat(0.f, f2{});
@@ -484,7 +518,7 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
       }
     };
     int i = 0;
-    if (odd) {  // orientation 1 in, 0 out
+    if (is_odd()) {  // orientation 1 in, 0 out
       const int la = layer_of(0);
       const bool pa = PERM && (lflag[la] & kFlagPerm);
       const float* wa = W + (int64_t)la * LF;
@@ -498,12 +532,15 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
       st_all(0, std::false_type{});
       i = 1;
     }
-    for (; i + 1 < L; i += 2) {
+    // the pair's blocks by a running pointer (one scalar add per pair; the
+    // second layer's are the first's at a constant offset)
+    constexpr int LS = INV ? -LF : LF;
+    const float* wa = W + (int64_t)layer_of(i) * LF;
+    for (; i + 1 < L; i += 2, wa += 2 * LS) {
       const int la = layer_of(i), lb = layer_of(i + 1);
       const bool pa = PERM && (lflag[la] & kFlagPerm);
       const bool pb = PERM && (lflag[lb] & kFlagPerm);
-      const float* wa = W + (int64_t)la * LF;
-      const float* wb = W + (int64_t)lb * LF;
+      const float* wb = wa + LS;
       SW<S::NC> cur, alt;
       sissue(cur, wa + lin_at<S, NETS, 0>());
       sp_step<D, H1, H2, INV, false, NETS, PERM, true, P>(v, ld, cur, alt, wa, wb, pa,
@@ -520,14 +557,30 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
     }
   };
   // tile: the lane's staged output rows in LDS (full tiles), or nullptr
-  auto loss = [&](const f2 (&v)[P][D], const f2 (&ld)[P], uint32_t lab, int nr,
-                  const float* tile, auto gather) {
+  // labels: the rows' int64 labels as loaded (full tiles: validated here,
+  // after the layer sweep, one 64-bit compare per row), or load_labels' packed
+  // bytes (ragged tile)
+  auto loss = [&](const f2 (&v)[P][D], const f2 (&ld)[P], const auto& labels, int nr,
+                  const float* tile, int kind, float det, auto gather) {
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       const int r = nr - 2 * p;
       constexpr int G = decltype(gather)::value;
-      pair_loss<D, G>(v[p], ld[p], lab >> (16 * p), r < 0 ? 0 : (r > 2 ? 2 : r), a.kind, a.det,
-                      lt0, lt1, lt2, tile + 2 * D * p);
+      bool ok[2];
+      int idx[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        if constexpr (G == 1) {
+          ok[q] = (uint64_t)labels[2 * p + q] < (uint64_t)D;
+          idx[q] = ok[q] ? (int)labels[2 * p + q] : 0;
+        } else {
+          const uint32_t b = (labels >> (16 * p + 8 * q)) & 0xffu;
+          ok[q] = b != 0xffu;
+          idx[q] = ok[q] ? (int)b : 0;
+        }
+      }
+      pair_loss<D, G>(v[p], ld[p], idx, ok, r < 0 ? 0 : (r > 2 ? 2 : r), kind, det, lt0, lt1, lt2,
+                      tile + 2 * D * p);
     }
   };
 
@@ -557,10 +610,10 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed
     f2 v[P][D];
     if constexpr (P == 1) {  // rows are in registers (reversed for an odd stack)
-      if (odd) read_pairs_wait<D, true>(sm, lane, v);
+      if (is_odd()) read_pairs_wait<D, true>(sm, lane, v);
       else read_pairs_wait<D, false>(sm, lane, v);
     } else {
-      if (odd) read_pairs<D, P, true>(sm, lane, v);
+      if (is_odd()) read_pairs<D, P, true>(sm, lane, v);
       else read_pairs<D, P, false>(sm, lane, v);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -568,14 +621,30 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
     if (ntr < 2) CNF_TR(1 + 2 * ntr);
 #endif
     const int64_t row0 = (int64_t)t * TR;
-    uint32_t lab = 0;
-    if constexpr (MODE == kLoss) lab = load_labels<D, P>(a.y + row0 + 2 * P * lane, 2 * P, y16);
+    int64_t lab[2 * P] = {};
+    if constexpr (MODE == kLoss) {
+      const int64_t* y = fresh_args()->y;
+      load_labels_raw<P>(y + row0 + 2 * P * lane, (reinterpret_cast<uintptr_t>(y) & 15) == 0,
+                         lab);
+    }
     f2 ld[P];
     compute(v, ld, row0, 2 * P);
+    // out / ld / kind / det: read here, after the layer sweep (fresh_args)
+    const KArgsPtr ka = fresh_args();
+    float* const out = ka->out;
+    float* const ldo = ka->ld;
     if constexpr (MODE == kLoss) {
+      int kind = ka->kind;
+      float det = ka->det;
+      // ... and waited for here, before the LDS traffic below: a scalar load
+      // shares the LDS counter, and a wait for `kind` placed after the staging
+      // writes would also wait for z[y], which the max / sum-exp should cover.
+      // (out / ld stay out of the asm: through it they would lose their
+      // address space and be stored to with flat instructions)
+      asm volatile("" : "+s"(kind), "+s"(det));
       // staged first: the loss reads z[y] back from the tile
       stage_pairs<D, P>(sm, lane, v);
-      loss(v, ld, lab, 2 * P, sm + 2 * P * D * lane, std::integral_constant<int, 1>{});
+      loss(v, ld, lab, 2 * P, sm + 2 * P * D * lane, kind, det, std::integral_constant<int, 1>{});
     }
 #ifdef CNF_SGPR_TRACE
     if (ntr < 2) CNF_TR(2 + 2 * ntr);
@@ -584,19 +653,27 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
 #endif
     // stage in the input tile (its rows are in registers), store lane-linear,
     // then let the next tile's DMA in once the staged reads have completed
-    if (a.out) {
+    if (out) {
       if (MODE != kLoss) stage_pairs<D, P>(sm, lane, v);
-      store_tile<TF>(a.out + row0 * D, sm, lane);
+      store_tile<TF>(out + row0 * D, sm, lane);
     }
-    if (a.ld) store_lds<P>(a.ld + row0 + 2 * P * lane, ld, 2 * P, al_ld);
+    if (ldo) store_lds<P>(ldo + row0 + 2 * P * lane, ld, 2 * P, align_of(ldo));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (t + nw < nfull) wave_dma<D, TR>(sm, in + (int64_t)(t + nw) * TF, lane);
+    if (t + nw < nfull) {
+      // (the tile's LDS address opaque here, or its five m0 values are
+      // computed in the prologue and carried across the loop)
+      typedef __attribute__((address_space(3))) float lds_f;
+      uint32_t sa = (uint32_t)(uintptr_t)(lds_f*)sm;
+      asm volatile("" : "+s"(sa));
+      wave_dma<D, TR>((lds_f*)(uintptr_t)sa, fresh_block()->in + (int64_t)(t + nw) * TF, lane);
+    }
   }
   // -------- the ragged last tile (B % TR rows): plain loads, masked stores --------
-  if (t == nfull && nfull < ntiles) {
+  if (t == nfull && fresh_block()->B % TR != 0) {
+    const float* __restrict__ in = fresh_block()->in;
     const int64_t row0 = (int64_t)t * TR;
     const int64_t r = row0 + 2 * P * lane;
-    const int64_t left_rows = B - r;
+    const int64_t left_rows = fresh_block()->B - r;
     const int nr = left_rows <= 0 ? 0 : (left_rows >= 2 * P ? 2 * P : (int)left_rows);
     f2 v[P][D];
     auto load_rows = [&](auto O_) {
@@ -609,19 +686,23 @@ __global__ __launch_bounds__(kWaves * 64, (waves_per_simd<MODE, ALL, PERM>())) v
           v[p][R<D, O>(k)].y = 2 * p + 1 < nr ? in[(r + 2 * p + 1) * D + k] : 0.f;
         }
     };
-    if (odd) load_rows(std::true_type{});
+    if (is_odd()) load_rows(std::true_type{});
     else load_rows(std::false_type{});
     uint32_t lab = 0;
-    if constexpr (MODE == kLoss) lab = load_labels<D, P>(a.y + r, nr, false);
+    if constexpr (MODE == kLoss) lab = load_labels<D, P>(fresh_args()->y + r, nr, false);
     f2 ld[P];
     compute(v, ld, row0, nr);
-    if constexpr (MODE == kLoss) loss(v, ld, lab, nr, sm, std::integral_constant<int, 0>{});
-    if (a.out) store_rows<D, P>(a.out + r * D, v, nr, 4);
-    if (a.ld) store_lds<P>(a.ld + r, ld, nr, 4);
+    const KArgsPtr ka = fresh_args();
+    float* const out = ka->out;
+    float* const ldo = ka->ld;
+    if constexpr (MODE == kLoss)
+      loss(v, ld, lab, nr, sm, ka->kind, ka->det, std::integral_constant<int, 0>{});
+    if (out) store_rows<D, P>(out + r * D, v, nr, 4);
+    if (ldo) store_lds<P>(ldo + r, ld, nr, 4);
   }
   CNF_TRC(1);
   CNF_TR(6);
-  if constexpr (MODE == kLoss) block_sum3<kWaves * 64>(lt0, lt1, lt2, smem, a.part);
+  if constexpr (MODE == kLoss) block_sum3<kWaves * 64>(lt0, lt1, lt2, smem, fresh_args()->part);
 }
 
 using KFn = void (*)(const float*, int64_t, const float*, const int32_t*, const int32_t*,

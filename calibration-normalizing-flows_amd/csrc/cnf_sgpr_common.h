@@ -90,6 +90,49 @@ __device__ __forceinline__ f2 fma_ws_clamp(const SW<NC>& w, int idx, f2 x, f2 ac
   return a;
 }
 
+// A whole 5 -> 5 Linear (the three Linears of the [5,5] conditioner at D=10:
+// row stride 6, rows [w0, b, w1 .. w4]) as ONE asm statement: the 25 FMAs of
+// fma_wb / fma_ws in the same input-major order with the same operands,
+// a[o] = neuron o, RELU: the clamp on each neuron's last FMA.  As one
+// statement per FMA the compiler's hazard recognizer put an s_nop 0 before
+// every input step: it cannot see into an asm statement, counts none of them
+// as a wait state, and so takes each FMA's read of its accumulator (written
+// five asm statements earlier) for a back-to-back use of a partial-register
+// write.  v_pk_fma_f32 writes whole registers and the hardware interlocks a
+// dependent VALU read, so there is nothing to wait for.  Outputs are
+// early-clobber: a[o] is written before the later inputs are read.
+#define CNF_L5_0(o) \
+  "v_pk_fma_f32 %[a" #o "], %[p" #o "0], %[x0], %[p" #o "0] op_sel:[0,0,1] op_sel_hi:[0,1,1]\n\t"
+#define CNF_L5_E(o, k, j, C) \
+  "v_pk_fma_f32 %[a" #o "], %[p" #o #j "], %[x" #k "], %[a" #o "] op_sel_hi:[0,1,1]" C "\n\t"
+#define CNF_L5_O(o, k, j, C)                                                                  \
+  "v_pk_fma_f32 %[a" #o "], %[p" #o #j "], %[x" #k "], %[a" #o "] op_sel:[1,0,0] op_sel_hi:[1,1,1]" \
+  C "\n\t"
+#define CNF_L5_ALL(M, ...) \
+  M(0, ##__VA_ARGS__) M(1, ##__VA_ARGS__) M(2, ##__VA_ARGS__) M(3, ##__VA_ARGS__) M(4, ##__VA_ARGS__)
+#define CNF_L5_TEXT(C)                                                                  \
+  CNF_L5_ALL(CNF_L5_0) CNF_L5_ALL(CNF_L5_E, 1, 1, "") CNF_L5_ALL(CNF_L5_O, 2, 1, "")     \
+  CNF_L5_ALL(CNF_L5_E, 3, 2, "") CNF_L5_ALL(CNF_L5_O, 4, 2, C)
+#define CNF_L5_P(o) \
+  [p##o##0] "s"(w.pair(6 * o)), [p##o##1] "s"(w.pair(6 * o + 2)), [p##o##2] "s"(w.pair(6 * o + 4))
+#define CNF_L5_ASM(C)                                                                          \
+  asm(CNF_L5_TEXT(C)                                                                           \
+      : [a0] "=&v"(a[0]), [a1] "=&v"(a[1]), [a2] "=&v"(a[2]), [a3] "=&v"(a[3]), [a4] "=&v"(a[4]) \
+      : [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]),         \
+        CNF_L5_P(0), CNF_L5_P(1), CNF_L5_P(2), CNF_L5_P(3), CNF_L5_P(4))
+template <bool RELU>
+__device__ __forceinline__ void lin5x5(const SW<2>& w, const f2 (&x)[5], f2 (&a)[5]) {
+  if constexpr (RELU) CNF_L5_ASM(" clamp");
+  else CNF_L5_ASM("");
+}
+#undef CNF_L5_ASM
+#undef CNF_L5_P
+#undef CNF_L5_TEXT
+#undef CNF_L5_ALL
+#undef CNF_L5_O
+#undef CNF_L5_E
+#undef CNF_L5_0
+
 // w * x, w = weights[idx] broadcast from its aligned SGPR pair (as fma_ws)
 template <int NC>
 __device__ __forceinline__ f2 mul_ws(const SW<NC>& w, int idx, f2 x) {
@@ -138,7 +181,8 @@ __device__ __forceinline__ void sissue(SW<NC>& r, const float* p) {
 // profiles/r05_ab_power.jsonl); sc1 nt measured the same as nt.
 constexpr int kDmaAux = 2;
 template <int D, int TR>
-__device__ __forceinline__ void wave_dma(float* sm, const float* __restrict__ src, int lane) {
+__device__ __forceinline__ void wave_dma(__attribute__((address_space(3))) float* sm,
+                                         const float* __restrict__ src, int lane) {
   constexpr int N4 = TR * D / 4, NI = (N4 + 63) / 64;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
@@ -147,6 +191,10 @@ __device__ __forceinline__ void wave_dma(float* sm, const float* __restrict__ sr
                                        (__attribute__((address_space(3))) void*)(sm + i * 256), 16,
                                        0, kDmaAux);
   }
+}
+template <int D, int TR>
+__device__ __forceinline__ void wave_dma(float* sm, const float* __restrict__ src, int lane) {
+  wave_dma<D, TR>((__attribute__((address_space(3))) float*)sm, src, lane);
 }
 
 // the lane's pairs from the LDS tile (one ds_read2_b32 per feature and pair)
@@ -362,6 +410,22 @@ __device__ __forceinline__ uint32_t load_labels(const int64_t* __restrict__ y, i
     packed |= (b0 | (b1 << 8)) << (16 * p);
   }
   return packed;
+}
+
+// The lane's 2P labels of a full tile as they are in memory (16-B loads when
+// aligned); whoever uses them checks 0 <= y < D (k_sgpr's loss lambda).
+template <int P>
+__device__ __forceinline__ void load_labels_raw(const int64_t* __restrict__ y, bool al16,
+                                                int64_t (&o)[2 * P]) {
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    if (al16) {
+      const longlong2 q = reinterpret_cast<const longlong2*>(y)[p];
+      o[2 * p] = q.x, o[2 * p + 1] = q.y;
+    } else {
+      o[2 * p] = y[2 * p], o[2 * p + 1] = y[2 * p + 1];
+    }
+  }
 }
 
 }  // namespace valu
