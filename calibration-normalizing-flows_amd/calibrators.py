@@ -19,8 +19,16 @@ objective / gradient evaluation is one cnf_scaling_loss_grad call
 (cnf_hip/scaling.py), and `predict` of a ROCm tensor is one
 cnf_scaling_predict launch that returns a ROCm fp32 tensor.
 
-Out of scope here: PAVCalibrator (sklearn isotonic regression on the host,
-calibrators.py:208-236) and TempScaler.
+PAVCalibrator (calibrators.py:208-236) keeps the reference's constructor
+`(logits, target)`: one isotonic regression per class on the class's softmax
+score.  NumPy inputs fit and predict in float64 on the host with the package's
+own NumPy isotonic fit (cnf_hip/pav.py: sklearn 1.7's steps restated, so no
+sklearn and no `np.float`); tensors are copied to the host for the fit.
+`predict` of a ROCm tensor is one cnf_pav_predict launch from the uploaded
+per-class tables and returns a ROCm fp32 tensor.  (The fit itself is not on
+the device yet: DESIGN.md section 7d.)
+
+Out of scope here: TempScaler.
 """
 import numpy as np
 import torch
@@ -265,6 +273,55 @@ class MLRCalibrator(_ScalingCalibrator):
 
     def predict_post(self, logits):
         return softmax(self.alpha * logits + self.gamma, axis=1)
+
+
+class PAVCalibrator(Calibrator):
+    """One isotonic regression (y_min=0, y_max=1, out_of_bounds='clip') per
+    class, one-vs-rest, on softmax(centred logits)[:, c] (calibrators.py:
+    208-236).  `models` holds each class's fitted points as host arrays
+    (X_thresholds_, y_thresholds_).  The fit is the package's NumPy isotonic
+    fit in float64 on the host (tensor inputs, ROCm ones included, are copied
+    there); `predict` of a ROCm tensor runs on the device."""
+
+    def __init__(self, logits, target):
+        if torch.is_tensor(logits):
+            logits = logits.detach().cpu().numpy()
+        if torch.is_tensor(target):
+            target = target.detach().cpu().numpy()
+        logits, target = np.asarray(logits, dtype=np.float64), np.asarray(target)
+        if target.shape != logits.shape:
+            labels = target.astype(int).reshape(-1)
+            if labels.size and (labels.min() < 0 or labels.max() >= logits.shape[1]):
+                raise ValueError("labels must lie in [0, %d)" % logits.shape[1])
+        with np.errstate(divide="ignore"):
+            super().__init__(logits, target)
+        self._model = None
+        self.fit(self.logits, self.target)
+
+    def fit(self, logits, target):
+        from cnf_hip import pav
+        self._model = None
+        self.models = pav.host_fit(softmax(logits, axis=1).astype(np.float64), np.asarray(target))
+
+    def _device_model(self, device):
+        from cnf_hip import pav
+        if self._model is None or self._model.thr_x.device != device:
+            self._model = pav.PavModel.from_host(self.models, device)
+        return self._model
+
+    def predict(self, logits):
+        from utils import ops
+        if ops._is_device(logits):
+            from cnf_hip import pav
+            return pav.predict(logits, self._device_model(logits.device), self.log_priors)
+        if torch.is_tensor(logits):
+            logits = logits.detach().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return super().predict(np.asarray(logits, dtype=np.float64))
+
+    def predict_post(self, logits):
+        from cnf_hip import pav
+        return pav.host_predict(self.models, softmax(logits, axis=1).astype(np.float64))
 
 
 def _native_stack(flow, dev, need_vjp=True):

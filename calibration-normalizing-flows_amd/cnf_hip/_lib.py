@@ -29,6 +29,7 @@ SCALE_SCALAR = 0  # CNF_SCALE_* (cnf_scaling_*): t = a*x + b, a one double
 SCALE_DIAG = 1    # t = w.x + b
 SCALE_FULL = 2    # t = x@W + b, D <= SCALE_FULL_MAX_DIM
 SCALE_FULL_MAX_DIM = 128
+PAV_LDS_ENTRIES = 2048  # cnf_pav_predict stages the tables in LDS when D * cap <= this
 
 # Every symbol include/cnf.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -40,6 +41,7 @@ EXPORTS = (
     "cnf_metrics_record_words", "cnf_metrics_workspace_bytes", "cnf_metrics",
     "cnf_scaling_sums_words", "cnf_scaling_workspace_bytes", "cnf_scaling_loss_grad",
     "cnf_scaling_predict",
+    "cnf_pav_predict",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -117,6 +119,7 @@ def _bind(lib):
         "cnf_scaling_loss_grad": (ctypes.c_int, [P, P, I32, I32, P, P, I32, I64, P, P,
                                                  ctypes.c_size_t, P]),
         "cnf_scaling_predict": (ctypes.c_int, [P, I32, I32, P, P, P, P, I64, P]),
+        "cnf_pav_predict": (ctypes.c_int, [P, I32, I64, P, P, P, I32, P, P, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),

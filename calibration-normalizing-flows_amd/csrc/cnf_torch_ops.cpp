@@ -28,6 +28,8 @@
 //       scaling fits                            calibrators.py:57-205, utils/ops.py:69-115
 //   cnf::scaling_predict(x, kind, a, b?, log_priors) -> probs
 //       Calibrator.predict of a fitted scaling map   calibrators.py:40-44
+//   cnf::pav_predict(x, thr_x, thr_y, n_thr, log_priors) -> probs
+//       PAVCalibrator.predict from per-class isotonic tables   calibrators.py:208-236
 //
 // `desc` is the descriptor as integers: [dim, n_layers, n_hidden, hidden[0..7],
 // scale, shift, strict_nan, options]; `perms` an optional host int64 [L, D]
@@ -311,6 +313,36 @@ Tensor scaling_predict_impl(const Tensor& x_, int64_t kind, const Tensor& a,
   return probs;
 }
 
+// x of the isotonic operators: a ROCm fp32 [B, D] tensor
+Tensor pav_rows(const Tensor& x, const char* op) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat32 && x.dim() == 2, "cnf::", op,
+              ": x must be a ROCm fp32 [B, D] tensor");
+  return x.contiguous();
+}
+
+Tensor pav_predict_impl(const Tensor& x_, const Tensor& thr_x, const Tensor& thr_y,
+                        const Tensor& n_thr, const Tensor& log_priors) {
+  DevGuard guard(x_.device());
+  Tensor x = pav_rows(x_, "pav_predict");
+  const int64_t B = x.size(0), D = x.size(1);
+  TORCH_CHECK(thr_x.dim() == 2 && thr_x.size(0) == D && thr_x.size(1) >= 1 &&
+                  thr_y.sizes() == thr_x.sizes(),
+              "cnf::pav_predict: thr_x and thr_y must be [D, cap] tensors");
+  const int64_t cap = thr_x.size(1);
+  const double* tx = dptr(thr_x, x, D * cap, "thr_x");
+  const double* ty = dptr(thr_y, x, D * cap, "thr_y");
+  TORCH_CHECK(n_thr.is_cuda() && n_thr.device() == x.device() &&
+                  n_thr.scalar_type() == torch::kInt32 && n_thr.is_contiguous() &&
+                  n_thr.numel() == D,
+              "cnf::pav_predict: n_thr must be a contiguous int32 [D] tensor on the device of x");
+  const double* lp = dptr(log_priors, x, D, "log_priors");
+  Tensor probs = torch::empty_like(x);
+  check("cnf_pav_predict",
+        cnf_pav_predict(x.data_ptr<float>(), (int32_t)D, B, tx, ty, n_thr.data_ptr<int32_t>(),
+                        (int32_t)cap, lp, probs.data_ptr<float>(), stream(x)));
+  return probs;
+}
+
 // Autograd: forward = one fused launch, backward = cnf_vjp (recomputes the
 // forward inside; nothing but x is saved).  INV: the inverse transform
 // (Flow.backward), backward = cnf_vjp_inverse.
@@ -406,6 +438,8 @@ TORCH_LIBRARY(cnf, m) {
   m.def("scaling_loss_grad(Tensor x, Tensor y, int kind, Tensor a, Tensor? b, bool want_grad, "
         "Tensor(a!) sums, Tensor(b!) workspace) -> ()");
   m.def("scaling_predict(Tensor x, int kind, Tensor a, Tensor? b, Tensor log_priors) -> Tensor");
+  m.def("pav_predict(Tensor x, Tensor thr_x, Tensor thr_y, Tensor n_thr, Tensor log_priors) "
+        "-> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
@@ -420,6 +454,7 @@ TORCH_LIBRARY_IMPL(cnf, CUDA, m) {
   m.impl("metrics", metrics_impl);
   m.impl("scaling_loss_grad", scaling_loss_grad_impl);
   m.impl("scaling_predict", scaling_predict_impl);
+  m.impl("pav_predict", pav_predict_impl);
 }
 
 TORCH_LIBRARY_IMPL(cnf, Autograd, m) {

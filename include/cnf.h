@@ -323,6 +323,31 @@ int cnf_scaling_predict(const float* x, int32_t kind, int32_t dim, const double*
                         const double* b, const double* log_priors, float* probs, int64_t B,
                         void* stream);
 
+/* Isotonic (pool-adjacent-violators) calibration, the reference's PAVCalibrator
+ * (calibrators.py:208-236): one sklearn IsotonicRegression(y_min=0, y_max=1,
+ * out_of_bounds='clip') per class on softmax(centred logits)[:, c].  The fit
+ * runs on the host (cnf_hip/pav.py); the device serves the prediction.
+ * 2 <= D <= CNF_MAX_DIM; B <= 2^26 (CNF_ERR_BATCH above).
+ *
+ * The model of class c is n_thr[c] points (thr_x[c][k], thr_y[c][k]), thr_x
+ * strictly increasing, thr_y non-decreasing (sklearn's X_thresholds_ /
+ * y_thresholds_), in arrays thr_x, thr_y [D][cap] of doubles, cap >= 1
+ * (CNF_ERR_DESC otherwise), and n_thr [D] of int32, all DEVICE memory. */
+
+/* Fused PAVCalibrator.predict (calibrators.py:40-44, 228-236), one launch: per
+ * row s = softmax(x - mean(x)) in float64; per class s_c clipped to
+ * [thr_x[c][0], thr_x[c][n-1]] and interpolated linearly between the points
+ * (SciPy interp1d's rule; n = min(n_thr[c], cap); n == 1 is the constant
+ * thr_y[c][0], n == 0 gives 0); each row divided by its sum (a row of zeros
+ * becomes NaN, as in the reference); probs = softmax(log(p + 1e-7) -
+ * log_priors), rounded once into fp32 probs [B][D] (ready for cnf_metrics).
+ * log_priors: D DEVICE doubles.  The tables are staged in LDS when
+ * D * cap <= 2048 and searched in global memory otherwise.  Enqueued on
+ * `stream`; no allocation, no host synchronisation; B == 0 launches nothing. */
+int cnf_pav_predict(const float* x, int32_t dim, int64_t B, const double* thr_x,
+                    const double* thr_y, const int32_t* n_thr, int32_t cap,
+                    const double* log_priors, float* probs, void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"

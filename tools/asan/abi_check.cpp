@@ -142,6 +142,46 @@ int main(int argc, char** argv) {
         for (int64_t w : rec) EXPECT(w == 0);  // nothing was written
       }
     }
+    // isotonic predict: one rejected argument each (range, batch, cap, NULL,
+    // alignment); nothing may be launched or written
+    {
+      const int32_t pdim = U(0, 4) == 0 ? U(-3, 400) : U(2, CNF_MAX_DIM);
+      const bool shape_ok = pdim >= 2 && pdim <= CNF_MAX_DIM;
+      alignas(8) double tx[4] = {7, 7, 7, 7}, ty[4] = {7, 7, 7, 7}, lp[4] = {0, 0, 0, 0};
+      alignas(8) int32_t nt[4] = {7, 7, 7, 7};
+      float out[4] = {7, 7, 7, 7};
+      const double* const odd = (const double*)((const char*)tx + 4);  // 4-aligned only
+      const int sp = cnf_pav_predict(dummy, pdim, nb, tx, ty, nt, 1, lp, out, nullptr);
+      EXPECT(sp < 0 && is_status(sp));
+      if (shape_ok) {
+        EXPECT(sp == CNF_ERR_BATCH);
+        EXPECT(cnf_pav_predict(dummy, pdim, (1LL << 26) + 1, tx, ty, nt, 1, lp, out, nullptr) ==
+               CNF_ERR_BATCH);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nt, 0, lp, out, nullptr) == CNF_ERR_DESC);
+        EXPECT(cnf_pav_predict(nullptr, pdim, 1, tx, ty, nt, 1, lp, out, nullptr) == CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, nullptr, ty, nt, 1, lp, out, nullptr) ==
+               CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, nullptr, nt, 1, lp, out, nullptr) ==
+               CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nullptr, 1, lp, out, nullptr) ==
+               CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nt, 1, nullptr, out, nullptr) ==
+               CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nt, 1, lp, nullptr, nullptr) ==
+               CNF_ERR_NULL);
+        EXPECT(cnf_pav_predict((const float*)((const char*)dummy + 2), pdim, 1, tx, ty, nt, 1, lp,
+                               out, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, odd, ty, nt, 1, lp, out, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, odd, nt, 1, lp, out, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, (const int32_t*)((const char*)nt + 2), 1,
+                               lp, out, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nt, 1, odd, out, nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(dummy, pdim, 1, tx, ty, nt, 1, lp, (float*)((char*)out + 2),
+                               nullptr) == CNF_ERR_ALIGN);
+        EXPECT(cnf_pav_predict(nullptr, pdim, 0, tx, ty, nt, 1, lp, nullptr, nullptr) == CNF_OK);
+      }
+      for (int k = 0; k < 4; ++k) EXPECT(tx[k] == 7 && ty[k] == 7 && nt[k] == 7 && out[k] == 7);
+    }
     delete perms;
   }
   EXPECT(cnf_param_count(nullptr, nullptr) == CNF_ERR_NULL);
