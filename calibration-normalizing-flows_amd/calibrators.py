@@ -28,6 +28,10 @@ sklearn and no `np.float`); tensors are copied to the host for the fit.
 per-class tables and returns a ROCm fp32 tensor.  (The fit itself is not on
 the device yet: DESIGN.md section 7d.)
 
+`Calibrator.detection_curves` scores predict() in the detection view (one-vs-rest
+log-likelihood ratios, empirical cross-entropy curves; cnf_hip/detection.py) in
+float64 on the host.
+
 Out of scope here: TempScaler.
 """
 import numpy as np
@@ -44,6 +48,25 @@ def _onehot(target, n_classes=None):
     out = np.zeros((target.shape[0], n))
     out[np.arange(target.shape[0]), target] = 1
     return out
+
+
+def _detection_curves(probs, target, priors, lims, bins):
+    """EceCurveSums of a probability matrix, in float64 on the host (a tensor,
+    e.g. a scaling calibrator's ROCm fp32 predict, is copied there)."""
+    from cnf_hip import detection
+    from utils import ops
+    if torch.is_tensor(probs):
+        probs = probs.detach().cpu().numpy()
+    probs = np.asarray(probs, dtype=np.float64)
+    D = int(probs.shape[1])
+    if torch.is_tensor(target):
+        target = target.detach().cpu().numpy()
+    target = np.asarray(target)
+    y = np.argmax(target, axis=1) if target.ndim == 2 else target.reshape(-1)
+    priors = np.full(D, 1. / D) if priors is None else np.asarray(priors, dtype=np.float64)
+    llr = ops.detection_log_likelihood_ratios(np.log(probs + 1e-7), priors)
+    return detection.ece_curve_sums(torch.from_numpy(llr), torch.as_tensor(y.astype(np.int64)),
+                                    detection.prior_axis(lims, bins))
 
 
 class Calibrator:
@@ -84,6 +107,15 @@ class Calibrator:
         return {"nll": M.neg_log_likelihood(probs, target),
                 "ece": M.expected_calibration_error(probs, target, bins=bins),
                 "accuracy": M.accuracy(probs, target), "n": int(probs.shape[0])}
+
+    def detection_curves(self, logits, target, priors=None, lims=(-2.5, 2.5), bins=100):
+        """The detection view of predict(logits) against `target` (labels or
+        one-hot rows) as cnf_hip.detection.EceCurveSums: the notebooks' steps
+        log(p + 1e-7), detection_log_likelihood_ratios with `priors` (uniform
+        1 / D by default) and the empirical cross-entropy curves of every
+        class over np.linspace(lims, num=bins) prior log10-odds.  The steps
+        after predict run in float64 on the host."""
+        return _detection_curves(self.predict(logits), target, priors, lims, bins)
 
 
 class DummyCalibrator(Calibrator):

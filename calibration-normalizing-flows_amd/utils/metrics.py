@@ -62,6 +62,32 @@ def empirical_cross_entropy(like_ratios, target, prior):
     return float(pos + neg)
 
 
+def empirical_cross_entropy_curve(like_ratios, target, range=(-2.5, 2.5), bins=100):
+    """(logprior_axis, ece): the numbers ECE_plot computes before it draws
+    (visualization.py:459-471): the axis np.linspace(range, num=bins) of prior
+    log10-odds and the empirical cross entropy at each point.  2-D ratios are
+    flattened and scored together against the one-hot target, as ECE_plot
+    does.  A list of ratio arrays gives ECE_plot_multi's [bins, len(list)]
+    matrix (visualization.py:530-541).  The reference's loop in float64 NumPy
+    on the host; tensors (ROCm ones included) are copied there."""
+    many = isinstance(like_ratios, (list, tuple))
+    axis = np.linspace(range[0], range[1], num=bins)
+    out = []
+    for lr in (like_ratios if many else [like_ratios]):
+        lr, t = _host(lr), _host(target)
+        if lr.ndim == 2:
+            if t.shape != lr.shape:
+                # width of the ratios, so a class the batch never draws keeps its column
+                t = (t.astype(np.int64).reshape(-1, 1) == np.arange(lr.shape[1])).astype(np.int32)
+            lr, t = lr.ravel(), t.ravel()
+        ece = np.zeros(axis.shape)
+        for i, logprior in enumerate(axis):
+            odds = 10 ** logprior
+            ece[i] = empirical_cross_entropy(lr, t, odds / (1. + odds))
+        out.append(ece)
+    return axis, (np.stack(out, axis=1) if many else out[0])
+
+
 def expected_calibration_error(probs, target, bins=15):
     """ECE of Guo et al. (arXiv:1706.04599) with equal-width confidence bins
     (low, high] (metrics.py:35-73)."""

@@ -12,6 +12,29 @@ def onehot_encode(target):
     return out
 
 
+def detection_log_likelihood_ratios(logits, priors):
+    """One-vs-rest log-likelihood ratios [B, D] of the logits under the class
+    priors (utils/ops.py:54-66):
+    -log(sum_{i != cls} priors[i] / (1 - priors[cls]) * exp(x_i - x_cls)).
+    The reference's double loop in float64 NumPy on the host, same summation
+    order; a tensor (a ROCm one included: there is no device kernel for the
+    ratios yet) is copied to the host.  Returns a float64 array."""
+    if hasattr(logits, "detach"):
+        logits = logits.detach().cpu().numpy()
+    if hasattr(priors, "detach"):
+        priors = priors.detach().cpu().numpy()
+    logits = np.asarray(logits, dtype=np.float64)
+    priors = np.asarray(priors, dtype=np.float64)
+    D = logits.shape[1]
+    acc = np.zeros(logits.shape)
+    for c in range(D):  # ascending i, skipping c: the reference's order of additions
+        for i in range(D):
+            if i != c:
+                acc[:, c] += priors[i] / (1 - priors[c]) * np.exp(logits[:, i] - logits[:, c])
+    with np.errstate(divide="ignore"):
+        return -np.log(acc)
+
+
 # ---- scaling calibrators (calibrators.py:57-205, utils/ops.py:69-115) ----
 SCALE_SCALAR, SCALE_DIAG, SCALE_FULL = 0, 1, 2   # CNF_SCALE_* of include/cnf.h
 
