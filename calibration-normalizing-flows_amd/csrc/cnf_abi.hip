@@ -254,7 +254,7 @@ int cnf_predict(const cnf_desc* desc, const void* prepared, const float* x,
   if (!prepared || !x || !log_priors || !probs) return CNF_ERR_NULL;
   auto mis = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3); };
   if (mis(x) || mis(probs) || mis(logdet) || mis(log_priors)) return CNF_ERR_ALIGN;
-  if (wide)  // k_wide's predict mode (centre + flow + softmax + prior correction)
+  if (wide)  // k_wide16's predict mode (centre + flow + softmax + prior correction)
     return wide_run(s, prepared, x, probs, logdet, B, false, (hipStream_t)stream, log_priors);
   return sgpr_run(s, prepared, x, probs, logdet, nullptr, B, false, (hipStream_t)stream, nullptr,
                   nullptr, 0, 0.f, nullptr, log_priors);

@@ -74,7 +74,7 @@ struct Shape {
   int tile_nop = 0;                  // padded S/T rows
   int tile_waves = 0;                // waves per block that fit LDS
   size_t tile_lds_bytes = 0;
-  // register-resident MFMA layout (cnf_wide.hip), appended after the tile region
+  // register-resident MFMA layout (cnf_wide16.hip), appended after the tile region
   int64_t wide_region = 0;           // float offset of the region in the weights region
   int64_t wide_floats = 0;           // floats of the region (0: shape not in its table)
   // natural (state_dict order) copy of every parameter, after the wide region:
@@ -117,8 +117,11 @@ int tile_run(const Shape& s, const void* prepared, const float* in, float* out, 
 
 int prepare_run(const Shape& s, const float* const* params, void* prepared, hipStream_t st);
 
-int64_t wide_layer_floats(const Shape& s);  // 0 when the shape has no k_wide instance
-bool wide_ok(const Shape& s);               // k_wide serves this descriptor's final outputs
+// the register-resident 16x16x4-tile family (cnf_wide16.hip)
+int64_t wide_layer_floats(const Shape& s);  // 0 when the shape has no k_wide16 instance
+// k_wide16 serves this descriptor's final outputs, and the fused training
+// sweeps (wide16_train_*) its reverse mode
+bool wide_ok(const Shape& s);
 int wide_prepare(const Shape& s, const float* const* params, void* prepared, hipStream_t st);
 int wide_run(const Shape& s, const void* prepared, const float* in, float* out, float* ld,
              int64_t B, bool inverse, hipStream_t st, const float* log_priors = nullptr);
@@ -161,12 +164,6 @@ int wide16_train_backward(const Shape& s, const void* prepared, const float* gz,
                           const float* gz_all, float* dx, const float* gld, const float* tape,
                           const uint32_t* tbits, float* gbuf, int64_t B, hipStream_t st);
 inline int64_t wide16_tbits_words(int64_t B) { return (B + 31) / 32 * 512; }  // per layer
-bool wide16_train_ok(const Shape& s);  // the fused training sweeps serve this descriptor
-// the 16x16x4-tile implementation behind wide_* (cnf_wide16.hip)
-int64_t wide16_layer_floats(const Shape& s);
-int wide16_prepare(const Shape& s, const float* const* params, void* prepared, hipStream_t st);
-int wide16_run(const Shape& s, const void* prepared, const float* in, float* out, float* ld,
-               int64_t B, bool inverse, hipStream_t st, const float* log_priors);
 
 // layer-at-a-time MFMA reverse mode of the tile family (cnf_wvjp.hip)
 bool wvjp_ok(const Shape& s);

@@ -92,10 +92,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 constexpr int kV2TR = 128;   // rows per wave tile (lane l: rows 2l, 2l+1)
-#ifndef CNF_V2_LMAX
-#define CNF_V2_LMAX 8
-#endif
-constexpr int kV2LMax = CNF_V2_LMAX;  // layers the register accumulators hold
+constexpr int kV2LMax = 8;   // layers the register accumulators hold
 constexpr int kV2SS = 68;    // stage row stride in floats (64 rows + pad, 16-B aligned)
 
 
@@ -217,29 +214,11 @@ __device__ __forceinline__ void vnet_fwd_sp(const float* wn, const f2* c, f2* h1
 // relu' from the recomputed activation h' = 2^-64 relu(pre) (the clamp-ReLU
 // output of vnet_fwd_sp: in [0, 1], 0 for a NaN pre-activation), as torch's
 // threshold_backward: drops g where h' = 0 and keeps it otherwise.
-// Default (2): clamp((h' 2^127) 2^127) * g, three packed ops per pair, no VCC
-// (the compare-and-select form, 0, costs two v_cmp + two v_cndmask per pair
-// plus the VCC hazard's wait states): 0.1765 -> 0.1750 ms per cfg2 step,
-// gradients bitwise unchanged.
-#ifndef CNF_V2_CLAMP_MASK
-#define CNF_V2_CLAMP_MASK 2
-#endif
-#if CNF_V2_CLAMP_MASK == 0
-__device__ __forceinline__ f2 relu_mask(f2 g, f2 h) {
-  return f2{h.x <= 0.f ? 0.f : g.x, h.y <= 0.f ? 0.f : g.y};
-}
-#elif CNF_V2_CLAMP_MASK == 1
-// A/B: the mask as clamp(h' 2^127) (packed; NaN clamps to 0) times g -- exact
-// for h' = 2^-64 h >= 2^-127, i.e. every pre-activation above 2^-63
-__device__ __forceinline__ f2 relu_mask(f2 g, f2 h) {
-  f2 m;
-  asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(m) : "v"(h), "s"(splat(0x1p127f, f2{})));
-  return g * m;
-}
-#else
-// clamp((h' 2^127) 2^127) times g -- exact for every h' > 0 (f32
-// denormals are kept: the smallest, 2^-149, maps to 2^105 before the clamp);
-// h' is the clamp-ReLU output, so h' in [0, 1] and 0 for a NaN pre-activation
+// As clamp((h' 2^127) 2^127) * g: three packed ops per pair, no VCC (a
+// compare-and-select costs two v_cmp + two v_cndmask per pair plus the VCC
+// hazard's wait states: 0.1765 -> 0.1750 ms per cfg2 step, gradients bitwise
+// unchanged).  Exact for every h' > 0: f32 denormals are kept, and the
+// smallest, 2^-149, maps to 2^105 before the clamp.
 __device__ __forceinline__ f2 relu_mask(f2 g, f2 h) {
   f2 m, u;
   const f2 k = splat(0x1p127f, f2{});
@@ -247,7 +226,6 @@ __device__ __forceinline__ f2 relu_mask(f2 g, f2 h) {
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(m) : "v"(u), "s"(k));
   return g * m;
 }
-#endif
 
 // Back-propagate one net: gout (d/d out) -> adds d/dc into gc and leaves the
 // gradient stack G = [g_a1, g_a2, gout] (pre-activation gradients).
@@ -326,25 +304,8 @@ __device__ __forceinline__ floatx4 wgrad_tile(float* st, const f2* G, const f2* 
   return acc;
 }
 
-// A/B: the x_T stash feature-major [L][DT][Bp] (whole-line stores) and
-// streaming (nt) stash traffic.  cfg2 step: row-major 0.1565-0.1577 ms,
-// feature-major 0.1581-0.1588, + nt stores 0.1647-0.1671, + nt loads too
-// 0.1643-0.1658 -- the stash is re-read one tile later and partly hits L2.
-#ifndef CNF_V2_STASH_FM
-#define CNF_V2_STASH_FM 0
-#endif
-#ifndef CNF_V2_STASH_NT
-#define CNF_V2_STASH_NT 0  // bit 0: streaming stash stores, bit 1: streaming stash loads
-#endif
-#ifndef CNF_V2_HLATE
-#define CNF_V2_HLATE 1  // the dW stack's 2^64 on h' applied once per wave (below)
-#endif
-#ifndef CNF_V2_TLATE
-#define CNF_V2_TLATE 0  // A/B: the t-net recompute after the s-net's backward step
-#endif
-#ifndef CNF_V2_WPS
-#define CNF_V2_WPS 2  // waves per SIMD the register budget is held to
-#endif
+
+constexpr int kV2WPS = 2;  // waves per SIMD the register budget is held to
 
 // parameter p (state_dict order of one layer) -> (G row i, H column j) of its
 // gradient in the (layer, net) tile, or -1 when the gradient is zero by the mask
@@ -408,10 +369,10 @@ __device__ __forceinline__ int cell_param(int i, int j) {
 }
 
 template <int D, int H1, int H2, int NETS, bool LOSS, bool PERM>
-__global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict__ W,
-                                                const int32_t* __restrict__ fq,
-                                                const int32_t* __restrict__ iq,
-                                                const int32_t* __restrict__ lflag, VArgs2 a) {
+__global__ __launch_bounds__(64, kV2WPS) void k_vjp2(const float* __restrict__ W,
+                                             const int32_t* __restrict__ fq,
+                                             const int32_t* __restrict__ iq,
+                                             const int32_t* __restrict__ lflag, VArgs2 a) {
   using S = SP<D, H1, H2>;
   constexpr int DT = S::DT, DC = S::DC, NC = S::NC;
   constexpr int LF = NETS * S::NF;
@@ -424,7 +385,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
   constexpr int kStage = 32 * kV2SS;
   const int lane = threadIdx.x;
   const int64_t B = a.B;
-  const int64_t Bp = (B + 1) & ~(int64_t)1;  // stash rows per feature (8-B aligned pairs)
   const int L = a.L;
   const int ntiles = (int)((B + kV2TR - 1) / kV2TR);
   const f2 zero = splat(0.f, f2{});
@@ -433,15 +393,10 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
   // the plain one (back-propagation): cnf_prepare's sp_region / vp_region
   const float* __restrict__ Wsp = W - (int64_t)L * LF;
   constexpr float kTwo64 = 0x1p64f;  // h = 2^64 h' (exact)
-#if CNF_V2_HLATE
   // H takes h' itself: the hidden columns of the accumulators are 2^-64 times
   // the gradient and get the 2^64 once, when the wave writes its partial (a
   // power-of-two scale commutes with every rounding of the sum until the
   // products fall below 2^-126, i.e. |g h| < 2^-62)
-  constexpr float kHs = 1.f;
-#else
-  constexpr float kHs = kTwo64;
-#endif
   floatx4 acc[kV2LMax][NETS];
 #pragma unroll
   for (int l = 0; l < kV2LMax; ++l)
@@ -484,26 +439,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
       for (int k = 0; k < DC; ++k) c[k] = v[R<D, O>(DT + k)];
       f2 h1[H1 ? H1 : 1], h2[H2 ? H2 : 1], t[DT], sv[DT];
       {  // x_T of this layer, rows r, r+1
-#if CNF_V2_STASH_FM
-        // feature-major [L][DT][Bp]: each 8-B store instruction writes 512
-        // contiguous bytes (whole lines), streamed past L2 (STASH_NT bit 0)
-        float* sp = a.stash + (int64_t)l * DT * Bp + r;
-        if (full) {
-#pragma unroll
-          for (int j = 0; j < DT; ++j) {
-            if (CNF_V2_STASH_NT & 1)
-              __builtin_nontemporal_store(v[R<D, O>(j)], reinterpret_cast<f2*>(sp + j * Bp));
-            else
-              *reinterpret_cast<f2*>(sp + j * Bp) = v[R<D, O>(j)];
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < DT; ++j) {
-            if (nr > 0) sp[j * Bp] = v[R<D, O>(j)].x;
-            if (nr > 1) sp[j * Bp + 1] = v[R<D, O>(j)].y;
-          }
-        }
-#else
         // row-major [L][B][DT]: 2*DT contiguous floats as (row r, row r+1)
         // pairs (8-B stores: the lane's slot starts 8-B aligned)
         float* sp = a.stash + ((int64_t)l * B + r) * DT;
@@ -517,7 +452,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
             if (nr > 1) sp[2 * j + 1] = v[R<D, O>(j)].y;
           }
         }
-#endif
       }
       const float* ws = Wsp + (int64_t)l * LF;
       vnet_fwd_sp<S, NC>(ws + (NETS == 2 ? S::NF : 0), c, h1, h2, t);
@@ -550,7 +484,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
     f2 gld = zero;
     auto seed = [&](auto O_) __attribute__((always_inline)) {
       constexpr bool O = decltype(O_)::value;
-#ifndef CNF_V2_SCALAR_SEED
       if constexpr (LOSS) {
         // Both rows as packed pairs (k_sgpr's pair_loss form): the max, the
         // exponentials e_j = exp(z_j - m) (kept: p_j = e_j / se, no second
@@ -632,56 +565,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
 #pragma unroll
           for (int j = 0; j < D; ++j) g[R<D, O>(j)] = o[j];
         }
-      } else
-#endif
-      if constexpr (LOSS) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          float z[D];
-#pragma unroll
-          for (int j = 0; j < D; ++j) z[j] = v[R<D, O>(j)][q];
-          float m = z[0];
-#pragma unroll
-          for (int j = 1; j < D; ++j) m = fmaxf(m, z[j]);
-          float se = 0.f;
-#pragma unroll
-          for (int j = 0; j < D; ++j) se += __builtin_amdgcn_exp2f((z[j] - m) * kL2E);
-          const float lse = m + __builtin_amdgcn_logf(se) * kLN2;
-          const uint32_t b = (lab >> (8 * q)) & 0xffu;
-          const bool ok = b != 0xffu, valid = q < nr;
-          const int yy = ok ? (int)b : 0;
-          uint32_t zb[D];
-#pragma unroll
-          for (int j = 0; j < D; ++j) zb[j] = __float_as_uint(z[j]);
-          const float lpy = __uint_as_float(sel_tree<D>(zb, yy, 0)) - lse;
-          const float ldq = NETS == 2 ? ld[q] : 0.f;  // plain weights: ld = sum(s)
-          float coef, ce_term, loss_row, gl;
-          if (a.kind == CNF_LOSS_CAL) {  // -(log(softmax(z)[y] + 1e-7) + ld)
-            const float py = __builtin_amdgcn_exp2f(lpy * kL2E);
-            ce_term = -__builtin_amdgcn_logf(py + kEps) * kLN2;
-            loss_row = ce_term - ldq;
-            coef = py / (py + kEps);
-            gl = -a.grad_scale;
-          } else {                       // CE(z, y) - det * ld
-            ce_term = -lpy;
-            loss_row = ce_term - a.det * ldq;
-            coef = 1.f;
-            gl = -a.det * a.grad_scale;
-          }
-          if (!ok) ce_term = loss_row = coef = __builtin_nanf("");
-          if (!valid) coef = gl = 0.f;
-#pragma unroll
-          for (int j = 0; j < D; ++j) {
-            const float pj = __builtin_amdgcn_exp2f((z[j] - lse) * kL2E);
-            g[R<D, O>(j)][q] = a.grad_scale * coef * (pj - (j == yy ? 1.f : 0.f));
-          }
-          gld[q] = gl;
-          if (valid) {
-            lt0 += loss_row;
-            lt1 += ce_term;
-            lt2 += ldq;
-          }
-        }
       } else {
 #pragma unroll
         for (int j = 0; j < D; ++j)
@@ -729,22 +612,6 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
       for (int j = 0; j < DT; ++j) gT[j] = g[R<D, Oi>(j)];
       f2 xT[DT];
       {
-#if CNF_V2_STASH_FM
-        const float* sp = a.stash + (int64_t)l * DT * Bp + r;
-        if (full) {
-#pragma unroll
-          for (int j = 0; j < DT; ++j) {
-            if (CNF_V2_STASH_NT & 2)
-              xT[j] = __builtin_nontemporal_load(reinterpret_cast<const f2*>(sp + j * Bp));
-            else
-              xT[j] = *reinterpret_cast<const f2*>(sp + j * Bp);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < DT; ++j)
-            xT[j] = f2{nr > 0 ? sp[j * Bp] : 0.f, nr > 1 ? sp[j * Bp + 1] : 0.f};
-        }
-#else
         const float* sp = a.stash + ((int64_t)l * B + r) * DT;
         if (full) {
 #pragma unroll
@@ -754,15 +621,12 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
           for (int j = 0; j < DT; ++j)
             xT[j] = f2{nr > 0 ? sp[2 * j] : 0.f, nr > 1 ? sp[2 * j + 1] : 0.f};
         }
-#endif
       }
       // recompute on the scaled weights: th / sh are 2^-64 h (relu' reads
       // their sign; the weight-gradient stack H takes 2^64 times them)
       const float* ws = Wsp + lofs;
       f2 th1[H1 ? H1 : 1], th2[H2 ? H2 : 1], t[DT];
-#if !CNF_V2_TLATE
       vnet_fwd_sp<S, NC>(ws + (NETS == 2 ? S::NF : 0), c, th1, th2, t);
-#endif
       f2 H[HS];
 #pragma unroll
       for (int k = 0; k < DC; ++k) H[k] = c[k];
@@ -786,16 +650,12 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
           for (int f = 0; f < GS; ++f) G[f] *= keep;
         }
 #pragma unroll
-        for (int m = 0; m < H1; ++m) H[DC + m] = sh1[m] * splat(kHs, f2{});
+        for (int m = 0; m < H1; ++m) H[DC + m] = sh1[m];
 #pragma unroll
-        for (int m = 0; m < H2; ++m) H[DC + H1 + m] = sh2[m] * splat(kHs, f2{});
+        for (int m = 0; m < H2; ++m) H[DC + H1 + m] = sh2[m];
         acc[l][0] = wgrad_tile<GS, HS>(st, G, H, lane, acc[l][0]);
       }
       {  // t-net: d/dt = g_T (before the e^s scaling of the s-net branch)
-#if CNF_V2_TLATE
-        // recomputed only now: th1 / th2 are not live across the s-net's step
-        vnet_fwd_sp<S, NC>(ws + (NETS == 2 ? S::NF : 0), c, th1, th2, t);
-#endif
         f2 G[GS];
         f2 gt[DT];
 #pragma unroll
@@ -806,9 +666,9 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
           for (int f = 0; f < GS; ++f) G[f] *= keep;
         }
 #pragma unroll
-        for (int m = 0; m < H1; ++m) H[DC + m] = th1[m] * splat(kHs, f2{});
+        for (int m = 0; m < H1; ++m) H[DC + m] = th1[m];
 #pragma unroll
-        for (int m = 0; m < H2; ++m) H[DC + H1 + m] = th2[m] * splat(kHs, f2{});
+        for (int m = 0; m < H2; ++m) H[DC + H1 + m] = th2[m];
         acc[l][NETS - 1] = wgrad_tile<GS, HS>(st, G, H, lane, acc[l][NETS - 1]);
       }
 #pragma unroll
@@ -856,7 +716,7 @@ __global__ __launch_bounds__(64, CNF_V2_WPS) void k_vjp2(const float* __restrict
   }
   // the lane's accumulator cells: C[i = 4 (lane/16) + e][j = lane % 16]
   const int j = lane & 15, i0 = 4 * (lane >> 4);
-  const float hsc = (CNF_V2_HLATE && j >= DC && j < DC + H1 + H2) ? kTwo64 : 1.f;
+  const float hsc = (j >= DC && j < DC + H1 + H2) ? kTwo64 : 1.f;
   // the cells' offsets within a net's block: the same for every (layer, net),
   // mapped once (laundered, so the mapping is not re-derived per store) and
   // gathered into one exec mask

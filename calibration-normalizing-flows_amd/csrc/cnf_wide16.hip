@@ -1,8 +1,8 @@
 // Wide coupling stacks on 16x16x4 f32 matrix-core tiles with every
 // activation in registers: the final-output forward / inverse / predict of
 // the CIFAR-100-class flows (D=100, hidden_size=[100,100], L=12: BASELINE.json
-// configs[3]).  Replaces k_wide's 32x32x2 tiles (cnf_wide.hip), whose 32-wide
-// output tiles and 2-deep K-steps padded a 100-unit layer to 128 outputs.
+// configs[3]).  (An earlier 32x32x2-tile family padded a 100-unit layer to 128
+// outputs with its 32-wide output tiles; DESIGN.md, "Removed A/B switches".)
 //
 // Reference semantics restated (paths in the reference repo):
 //   MLP.forward                 flows/utils.py:26-31
@@ -24,7 +24,7 @@
 // takes ceil(U / 4) steps (100 units: 25, not 28); an output takes ceil(U / 16)
 // M-tiles (100: 7 = 112 slots, not 4 x 32 = 128).  Biases initialise the
 // accumulators (no bias K-step).  Issued MACs per cfg4 layer: 1.17x the
-// reference's, against k_wide's 1.39x.
+// reference's (32x32x2 tiles: 1.39x).
 //
 // The state: the conditioning half (features DT..D-1, the masked input the
 // nets read, flows/flows.py:81-86) in tiles [0, CS/16), the transformed half
@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 #include <utility>
 
 #include "cnf_internal.h"
@@ -46,72 +45,32 @@ namespace {
 
 typedef float v4 __attribute__((ext_vector_type(4)));
 
-#ifndef CNF_W16_PMAX
-#define CNF_W16_PMAX 16  // deepest A-operand ring
-#endif
-#ifndef CNF_W16_FWD_P16
-#define CNF_W16_FWD_P16 0  // the same for the forward streams: measured no change (2545 vs 2547 us cfg4 forward), spills the training forward; off
-#endif
-#ifndef CNF_W16_BWD_P16
-#define CNF_W16_BWD_P16 1  // pad the reverse stream per layer to 16-step multiples
-#endif
+constexpr int kPMax = 16;  // deepest A-operand ring
 
-// A-stream layout: 0 fragment-major (step T, lane l at 64 T + l: one dword
-// load per lane and K-step); 1 four steps interleaved per lane (steps 4j..4j+3
-// of lane l at 256 j + 4 l: one 16-B load per lane every four K-steps)
-#ifndef CNF_W16_PACK4
-#define CNF_W16_PACK4 1
-#endif
-#ifndef CNF_W16_REFILL  // packed layout: steps per refill load (4: 16 B, 2: 8 B per lane)
-#define CNF_W16_REFILL 4
-#endif
-constexpr bool kPack4 = CNF_W16_PACK4 != 0;
-constexpr int kLaneStride = kPack4 ? 4 : 1;  // a lane's first float of a step group
+// A-stream layout: four steps interleaved per lane (steps 4j..4j+3 of lane l at
+// 256 j + 4 l: one 16-B load per lane every four K-steps)
+constexpr int kLaneStride = 4;  // a lane's first float of a step group
 // float offset (lane 0) of stream step T
-__host__ __device__ constexpr int afrag(int T) { return kPack4 ? (T >> 2) * 256 + (T & 3) : T * 64; }
+__host__ __device__ constexpr int afrag(int T) { return (T >> 2) * 256 + (T & 3); }
 
 constexpr int kRows = 32;   // rows per wave (two row groups of 16)
 constexpr int kWaves = 4;   // waves per block
-// row groups per wave of the inference kernel (k_wide16): 2 -> 32 rows per
-// wave at 2 waves per SIMD; 4 -> 64 rows per wave at 1 wave per SIMD
-#ifndef CNF_W16_RUN_RG
-#define CNF_W16_RUN_RG 2
-#endif
-constexpr int kRunRG = CNF_W16_RUN_RG, kRunRows = 16 * kRunRG;
-static_assert(kRunRG == 2 || kRunRG == 4, "CNF_W16_RUN_RG: 2 or 4");
 
 // the slot of unit u (and, the map being an involution, the unit of slot u)
 __host__ __device__ constexpr int qslot(int u) {
   return 16 * (u >> 4) + 4 * (u & 3) + ((u & 15) >> 2);
 }
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-// a layer's stream steps with its pads (16-step multiples when p16, 4-step
-// multiples for the packed layout)
-__host__ __device__ constexpr int pad_ls(int ls, bool p16) {
-  return p16 ? cdiv(ls, 16) * 16 : (kPack4 ? cdiv(ls, 4) * 4 : ls);
-}
-// k_wide16's A stream through LDS (A/B): the block's four waves copy the stream
-// by LDS-DMA in chunks of kAC steps (one 1-KiB piece per wave) into two stages,
-// and refill their rings from LDS; forward streams padded to 2 kAC steps
-#ifndef CNF_W16_LDSA
-#define CNF_W16_LDSA 1
-#endif
-#ifndef CNF_W16_LDSA_CHUNK  // steps per LDS chunk (a multiple of 16: one 1-KiB piece per wave per 16)
-#define CNF_W16_LDSA_CHUNK 16
-#endif
-constexpr int kAC = CNF_W16_LDSA_CHUNK;
-#ifndef CNF_W16_LDSA_PMAX  // k_wide16's ring depth with the LDS stream (LDS latency is short)
-#define CNF_W16_LDSA_PMAX 8
-#endif
-__host__ __device__ constexpr int pad_fwd(int ls) {
-  return CNF_W16_LDSA ? cdiv(ls, 2 * kAC) * 2 * kAC : pad_ls(ls, CNF_W16_FWD_P16);
-}
+// k_wide16's A stream through LDS: the block's four waves copy the stream by
+// LDS-DMA in chunks of kAC steps (one 1-KiB piece per wave) into two stages,
+// and refill their rings from LDS; forward streams padded to 2 kAC steps (the
+// training forward reads the same stream straight from memory)
+constexpr int kAC = 16;  // steps per LDS chunk (a multiple of 16: one 1-KiB piece per wave per 16)
+constexpr int kLdsAPMax = 8;  // k_wide16's ring depth with the LDS stream (LDS latency is short)
+__host__ __device__ constexpr int pad_fwd(int ls) { return cdiv(ls, 2 * kAC) * 2 * kAC; }
+// the reverse sweep's stream steps per layer with their pads (16-step multiples)
+__host__ __device__ constexpr int pad_bwd(int ls) { return cdiv(ls, 16) * 16; }
 extern __shared__ __attribute__((aligned(16))) float w16_dyn[];
-// the training forward sweep's A stream through LDS as k_wide16's (A/B): its
-// chunk waits (vmcnt(0)) also cover the tape stores issued since the last one
-#ifndef CNF_W16_TRAIN_LDSA
-#define CNF_W16_TRAIN_LDSA 0
-#endif
 
 // Compile-time geometry of one conditioner MLP (H = 0: absent hidden layer).
 template <int D, int H1, int H2>
@@ -139,12 +98,17 @@ struct G16 {
   static constexpr bool kLdsA = false;
   static constexpr int T1 = H1 > 0 ? cdiv(H1, 16) : 1, T2 = H2 > 0 ? cdiv(H2, 16) : 1;
 };
-// k_wide16's geometry when its A stream comes through LDS
+// floats of a block's per-wave state areas, rounded to 64 (k_wide16's A stages
+// follow them)
+__host__ __device__ constexpr int state_floats(int D) {
+  return cdiv(kWaves * (kRows * (D | 1) + D), 64) * 64;
+}
+// k_wide16's geometry: its A stream comes through LDS
 template <int D, int H1, int H2>
 struct G16L : G16<D, H1, H2> {
-  static constexpr bool kLdsA = CNF_W16_LDSA != 0;
+  static constexpr bool kLdsA = true;
   // floats of the waves' state areas (the A stages follow)
-  static constexpr int kStateFloats = cdiv(kWaves * (kRunRows * (D | 1) + D), 64) * 64;
+  static constexpr int kStateFloats = state_floats(D);
 };
 
 // feature of state slot s (-1: padding)
@@ -163,19 +127,18 @@ __device__ __forceinline__ int feat_of(int s) {
 // [6, pmax] (the ring runs on across layers)
 __host__ __device__ constexpr int ring16(int ls, int pmax) {
   for (int p = pmax; p >= 6; --p)
-    if (ls % p == 0 && (!kPack4 || p % 4 == 0)) return p;
-  return kPack4 ? 4 : 1;
+    if (ls % p == 0 && p % 4 == 0) return p;
+  return 4;
 }
 
-// the ring's refill at stream step T (fragment T + P into the slot step T
-// just used); packed: every fourth step, the four slots steps T-3..T used
-// (a 16-B load per lane)
+// the ring's refill at stream step T: every fourth step, fragments T-3+P..T+P
+// into the four slots steps T-3..T just used (a 16-B load per lane)
 template <class G, int NETS, int P, int T>
 __device__ __forceinline__ void refill(float (&ring)[P], const float* __restrict__ a,
                                        const float* __restrict__ an) {
   constexpr int LS = G::template lsp<NETS>();  // stream steps per layer (pads included)
   if constexpr (G::kLdsA) {
-    static_assert(kPack4 && P % 4 == 0 && P <= kAC && LS % (2 * kAC) == 0, "LDS A stream");
+    static_assert(P % 4 == 0 && P <= kAC && LS % (2 * kAC) == 0, "LDS A stream");
     if constexpr ((T & 3) == 3) {
       constexpr int S0 = T - 3 + P;  // first step refilled
       const int lane = threadIdx.x & 63;
@@ -200,10 +163,7 @@ __device__ __forceinline__ void refill(float (&ring)[P], const float* __restrict
       ring[(T - 1) % P] = v[2];
       ring[T % P] = v[3];
     }
-  } else if constexpr (!kPack4) {
-    if constexpr (T + P < LS) ring[T % P] = a[afrag(T + P)];
-    else ring[T % P] = an[afrag(T + P - LS)];
-  } else if constexpr (CNF_W16_REFILL == 4 && (T & 3) == 3) {
+  } else if constexpr ((T & 3) == 3) {
     static_assert(P % 4 == 0 && LS % 4 == 0, "packed A stream: ring and layer in 4-step groups");
     constexpr int S0 = T - 3 + P;  // first step refilled (a multiple of 4)
     const v4 v = *reinterpret_cast<const v4*>(S0 < LS ? a + afrag(S0) : an + afrag(S0 - LS));
@@ -211,13 +171,6 @@ __device__ __forceinline__ void refill(float (&ring)[P], const float* __restrict
     ring[(T - 2) % P] = v[1];
     ring[(T - 1) % P] = v[2];
     ring[T % P] = v[3];
-  } else if constexpr (CNF_W16_REFILL == 2 && (T & 1) == 1) {
-    static_assert(P % 4 == 0 && LS % 4 == 0, "packed A stream: ring and layer in 4-step groups");
-    constexpr int S0 = T - 1 + P;  // first step refilled (even)
-    typedef float v2 __attribute__((ext_vector_type(2)));
-    const v2 v = *reinterpret_cast<const v2*>(S0 < LS ? a + afrag(S0) : an + afrag(S0 - LS));
-    ring[(T - 1) % P] = v[0];
-    ring[T % P] = v[1];
   }
 }
 
@@ -470,7 +423,7 @@ __device__ __forceinline__ void row_predict16(float* st, int S, int lane,
 
 // MODE 0 forward, 1 inverse, 2 predict (centre + forward + calibrated probs)
 template <int D, int H1, int H2, int MODE, int NETS>
-__global__ __launch_bounds__(64 * kWaves, kRunRG == 2 ? 2 : 1) void k_wide16(
+__global__ __launch_bounds__(64 * kWaves, 2) void k_wide16(
     const float* __restrict__ W, const int32_t* __restrict__ qtab,
     const float* __restrict__ in, float* __restrict__ out, float* __restrict__ ld_out,
     int64_t B, int L, const float* __restrict__ lpri) {
@@ -483,50 +436,47 @@ __global__ __launch_bounds__(64 * kWaves, kRunRG == 2 ? 2 : 1) void k_wide16(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // SGPR: row0, descriptors
-  const int64_t row0 = ((int64_t)blockIdx.x * kWaves + wave) * kRunRows;
-  // waves synchronise only with themselves (LDS A stream: the whole block
-  // takes part in every chunk; a wave past the batch computes zero rows)
-  if (!G::kLdsA && row0 >= B) return;
-  const int nrows = (int)((B - row0) < kRunRows ? (B - row0) : kRunRows);
-  float* st = smem + wave * (kRunRows * S + D);
-  int* qs = reinterpret_cast<int*>(st + kRunRows * S);
+  const int64_t row0 = ((int64_t)blockIdx.x * kWaves + wave) * kRows;
+  // no early exit: the whole block takes part in every chunk of the LDS A
+  // stream; a wave past the batch (nrows <= 0) computes zero rows, stores none
+  const int nrows = (int)((B - row0) < kRows ? (B - row0) : kRows);
+  float* st = smem + wave * (kRows * S + D);
+  int* qs = reinterpret_cast<int*>(st + kRows * S);
 
   // rows -> LDS (coalesced) -> slots
   const float* src = in + row0 * D;
-  for (int i = lane; i < kRunRows * D; i += 64) {
+  for (int i = lane; i < kRows * D; i += 64) {
     const int r = i / D, f = i - r * D;
     st[r * S + f] = r < nrows ? src[i] : 0.f;
   }
   wsync();
   if constexpr (MODE == 2) {  // x - mean(x) per row (calibrators.py:42)
-    for (int rb = 0; rb < kRunRows; rb += 32) row_centre16<D>(st + rb * S, S, lane);
+    // (the row helpers take 32 rows a call; one trip at kRows = 32, written as
+    // the loop the compiler has always seen: without it the predict builds'
+    // instruction schedule changes)
+    for (int rb = 0; rb < kRows; rb += 32) row_centre16<D>(st + rb * S, S, lane);
     wsync();
   }
-  v4 X[XT][kRunRG];
+  v4 X[XT][2];
   get_state<G>(st, S, nullptr, X, lane);
   wsync();
 
   // the A stream: one ring for the whole launch, P fragments ahead of the MFMAs
-  constexpr int P = ring16(LSP, G::kLdsA ? CNF_W16_LDSA_PMAX : CNF_W16_PMAX);
+  constexpr int P = ring16(LSP, kLdsAPMax);
   float ring[P];
-  {
+  {  // chunks 0 and 1 of the first layer, then the ring from LDS
     const float* a0 = W + (int64_t)(INV ? L - 1 : 0) * LF + kLaneStride * lane;
-    if constexpr (G::kLdsA) {  // chunks 0 and 1 of the first layer, then the ring from LDS
-      float* stage = w16_dyn + G::kStateFloats;
+    float* stage = w16_dyn + G::kStateFloats;
 #pragma unroll
-      for (int k = 0; k < 2 * kAC / 16; ++k)
-        __builtin_amdgcn_global_load_lds(const_cast<float*>(a0 + 256 * (4 * k + wave)),
-                                         stage + 256 * (4 * k + wave), 16, 0, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+    for (int k = 0; k < 2 * kAC / 16; ++k)
+      __builtin_amdgcn_global_load_lds(const_cast<float*>(a0 + 256 * (4 * k + wave)),
+                                       stage + 256 * (4 * k + wave), 16, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
 #pragma unroll
-      for (int j = 0; j < P; ++j) ring[j] = stage[afrag(j) + 4 * lane];
-    } else {
-#pragma unroll
-      for (int j = 0; j < P; ++j) ring[j] = a0[afrag(j)];
-    }
+    for (int j = 0; j < P; ++j) ring[j] = stage[afrag(j) + 4 * lane];
   }
-  float ld[kRunRG] = {};
+  float ld[2] = {};
   for (int stp = 0; stp < L; ++stp) {
     const int l = INV ? L - 1 - stp : stp;
     const int ln = stp + 1 < L ? (INV ? l - 1 : l + 1) : l;  // last layer: harmless re-read
@@ -535,29 +485,29 @@ __global__ __launch_bounds__(64 * kWaves, kRunRG == 2 ? 2 : 1) void k_wide16(
     const float* __restrict__ wl = W + (int64_t)l * LF + kLaneStride * lane;
     const float* __restrict__ wn = W + (int64_t)ln * LF + kLaneStride * lane;
     const float* __restrict__ bl = W + (int64_t)l * LF + LA;  // the layer's bias blocks
-    v4 Tv[TT][kRunRG];
-    EpOut<false, TT, kRunRG> et{Tv};
+    v4 Tv[TT][2];
+    EpOut<false, TT, 2> et{Tv};
     if constexpr (NETS == 2) {  // stream order (prepare): t-net, then s-net
       net<G, 2, 0>(ring, wl, wn, bl, X, et, lane);
-      EpAffine<INV, XT, CT, TT, kRunRG> ea{X, Tv, ld};
+      EpAffine<INV, XT, CT, TT, 2> ea{X, Tv, ld};
       net<G, 2, 1>(ring, wl, wn, bl + G::NB, X, ea, lane);
     } else {
       net<G, 1, 0>(ring, wl, wn, bl, X, et, lane);
 #pragma unroll
       for (int t = 0; t < TT; ++t)
 #pragma unroll
-        for (int g = 0; g < kRunRG; ++g) X[CT + t][g] = INV ? X[CT + t][g] - Tv[t][g] : X[CT + t][g] + Tv[t][g];
+        for (int g = 0; g < 2; ++g) X[CT + t][g] = INV ? X[CT + t][g] - Tv[t][g] : X[CT + t][g] + Tv[t][g];
     }
     pad_steps<G, NETS, P>(ring, wl, wn, std::make_integer_sequence<int, LSP - NETS * G::steps()>{});
     if constexpr (!INV) relayout<G>(st, qs, S, q, X, lane);  // perm then flip
   }
-  if constexpr (G::kLdsA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA outlives the block
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA outlives the block
 
   // slots -> LDS rows -> coalesced stores
   put_state<G>(st, S, X, lane);
   wsync();
   if constexpr (MODE == 2) {
-    for (int rb = 0; rb < kRunRows; rb += 32) row_predict16<D>(st + rb * S, S, lane, lpri);
+    for (int rb = 0; rb < kRows; rb += 32) row_predict16<D>(st + rb * S, S, lane, lpri);
     wsync();
   }
   if (out) {
@@ -569,13 +519,13 @@ __global__ __launch_bounds__(64 * kWaves, kRunRG == 2 ? 2 : 1) void k_wide16(
   }
   // a row's log-det terms are spread over the four lane groups (l >> 4)
 #pragma unroll
-  for (int g = 0; g < kRunRG; ++g) {
+  for (int g = 0; g < 2; ++g) {
     ld[g] += __shfl_xor(ld[g], 16);
     ld[g] += __shfl_xor(ld[g], 32);
   }
   if (ld_out && lane < 16) {
 #pragma unroll
-    for (int g = 0; g < kRunRG; ++g)
+    for (int g = 0; g < 2; ++g)
       if (16 * g + lane < nrows) ld_out[row0 + 16 * g + lane] = ld[g];
   }
 }
@@ -610,7 +560,7 @@ struct G16T {
   // steps, can then be 16 deep instead of 12, and every tape / G access gets 16
   // K-steps to complete before a ring wait covers it (vmcnt counts in order).
   template <int NETS>
-  static constexpr int lsp() { return pad_ls(NETS * steps(), CNF_W16_BWD_P16); }
+  static constexpr int lsp() { return pad_bwd(NETS * steps()); }
 };
 
 
@@ -644,16 +594,10 @@ struct Tape16 {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-// A/B knobs: which tape traffic runs (never shipped changed) -- bit 0 the
-// XC / XT / S stores, 1 the hidden stores, 2 the reverse sweep's G stores --
-// and the stores' cache-policy bits (nt measured 0.45 ms faster per forward
-// sweep and 0.36 ms per reverse sweep at cfg4 than default-policy stores)
-#ifndef CNF_W16_TAPE
-#define CNF_W16_TAPE 15
-#endif
-#ifndef CNF_W16_STORE_AUX
-#define CNF_W16_STORE_AUX 2  // nt: streaming stores (tape reuse is a whole sweep away)
-#endif
+// the tape / G stores' cache-policy bits: nt, streaming stores (tape reuse is
+// a whole sweep away; measured 0.45 ms faster per forward sweep and 0.36 ms
+// per reverse sweep at cfg4 than default-policy stores)
+constexpr int kStoreAux = 2;
 
 // One wave's block of a wave-tiled [B][W] array (the tape and G layouts):
 // rows in blocks of 32, a block's 32 x W floats as [W / 16 tiles][2 row
@@ -667,19 +611,15 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 struct Rows16 {
   __amdgpu_buffer_rsrc_t rs;
   int voff[2];
-  // live = false: a wave wholly past the batch (it still runs the block's
-  // stream for the LDS A-stream barriers): every access falls outside the
-  // descriptor (stores dropped, loads read 0)
-  __device__ __forceinline__ Rows16(const float* block, int W, int lane, bool live = true) {
-    rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(block), 0, live ? kRows * W * 4 : 0,
-                                           0x00020000);
+  __device__ __forceinline__ Rows16(const float* block, int W, int lane) {
+    rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(block), 0, kRows * W * 4, 0x00020000);
 #pragma unroll
     for (int g = 0; g < 2; ++g) voff[g] = (g * 256 + (lane & 15) * 16 + 4 * (lane >> 4)) * 4;
   }
   // off: the tile's first slot (floats into the row, a multiple of 16)
   __device__ __forceinline__ void store(const v4& v, int g, int off) const {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), rs, voff[g], off * 128,
-                                           CNF_W16_STORE_AUX);
+                                           kStoreAux);
   }
   __device__ __forceinline__ v4 load(int g, int off) const {
     return __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[g], off * 128, 0));
@@ -745,7 +685,6 @@ struct EpTape {
 // one burst of T tiles into part OFF (slot ONE of the part set to 1)
 template <int OFF, int T, int ONE>
 __device__ __forceinline__ void tape_tiles(const Rows16& tp, const v4 (&h)[T][2], int lane) {
-  if (!(CNF_W16_TAPE & 2)) return;
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll
@@ -778,7 +717,7 @@ struct EpAffineTape {
   __device__ __forceinline__ void put(v4 (&s)[2]) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      if (CNF_W16_TAPE & 1) tp.store(s[g], g, OFF + 16 * MO);
+      tp.store(s[g], g, OFF + 16 * MO);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float sv = s[g][q];
@@ -905,8 +844,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_wtrain16_fwd(
     const float* __restrict__ W, const int32_t* __restrict__ qtab, const float* __restrict__ in,
     float* __restrict__ zst, float* __restrict__ ld_out, float* __restrict__ tape,
     uint32_t* __restrict__ tbits, int64_t B, int L, int Cp, int Dp, SeedArgs sa) {
-  using G = std::conditional_t<CNF_W16_TRAIN_LDSA != 0 && kRunRows == kRows, G16L<D, H1, H2>,
-                               G16<D, H1, H2>>;
+  using G = G16<D, H1, H2>;
   using TP = Tape16<D, H1, H2, NETS>;
   constexpr int XT = G::XT, CT = G::CT, TT = G::TT;
   constexpr int S = D | 1;
@@ -917,11 +855,8 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_wtrain16_fwd(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // SGPR: row0, descriptors
   const int64_t row0 = ((int64_t)blockIdx.x * kWaves + wave) * kRows;
-  // (LDS A stream: the whole block meets every chunk barrier; a wave past the
-  // batch runs the stream on zero rows with its tape descriptors empty)
-  if (!G::kLdsA && row0 >= B) return;
-  const bool live = row0 < B;
-  const int nrows = !live ? 0 : (int)((B - row0) < kRows ? (B - row0) : kRows);
+  if (row0 >= B) return;  // waves synchronise only with themselves
+  const int nrows = (int)((B - row0) < kRows ? (B - row0) : kRows);
   const int64_t nwb = (B + kRows - 1) / kRows;
   float* st = smem + wave * (kRows * S + D);
   int* qs = reinterpret_cast<int*>(st + kRows * S);
@@ -936,49 +871,34 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_wtrain16_fwd(
   get_state<G>(st, S, nullptr, X, lane);
   wsync();
 
-  constexpr int P = ring16(LSP, G::kLdsA ? CNF_W16_LDSA_PMAX : CNF_W16_PMAX);
+  constexpr int P = ring16(LSP, kPMax);
   float ring[P];
-  if constexpr (G::kLdsA) {  // chunks 0 and 1 of the first layer, then the ring from LDS
-    float* stage = w16_dyn + G::kStateFloats;
 #pragma unroll
-    for (int k = 0; k < 2 * kAC / 16; ++k)
-      __builtin_amdgcn_global_load_lds(const_cast<float*>(W + kLaneStride * lane + 256 * (4 * k + wave)),
-                                       stage + 256 * (4 * k + wave), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < P; ++j) ring[j] = stage[afrag(j) + 4 * lane];
-  } else {
-#pragma unroll
-    for (int j = 0; j < P; ++j) ring[j] = W[kLaneStride * lane + afrag(j)];
-  }
+  for (int j = 0; j < P; ++j) ring[j] = W[kLaneStride * lane + afrag(j)];
   float ld[2] = {0.f, 0.f};
   for (int l = 0; l < L; ++l) {
     const int ln = l + 1 < L ? l + 1 : l;
     const float* __restrict__ wl = W + (int64_t)l * LF + kLaneStride * lane;
     const float* __restrict__ wn = W + (int64_t)ln * LF + kLaneStride * lane;
     const float* __restrict__ bl = W + (int64_t)l * LF + LA;
-    const Rows16 tp(tape + ((int64_t)l * nwb * kRows + (live ? row0 : 0)) * TP::RW, TP::RW, lane,
-                    live);
+    const Rows16 tp(tape + ((int64_t)l * nwb * kRows + row0) * TP::RW, TP::RW, lane);
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
 #pragma unroll
       for (int t = 0; t < CT; ++t) {
         v4 v = X[t][g];
         if ((OC >> 4) == t && (lane >> 4) == ((OC >> 2) & 3)) v[OC & 3] = 1.f;
-        if (CNF_W16_TAPE & 1) tp.store(v, g, TP::XC + 16 * t);
+        tp.store(v, g, TP::XC + 16 * t);
       }
 #pragma unroll
       for (int t = 0; t < TT; ++t)
-        if (CNF_W16_TAPE & 1) tp.store(X[CT + t][g], g, TP::XTo + 16 * t);
+        tp.store(X[CT + t][g], g, TP::XTo + 16 * t);
     }
     tape_ones_tile<TP::XC, CT, OC>(tp, lane);
     v4 Tv[TT][2];
     EpOut<false, TT> et{Tv};
     // this wave's relu' bits: 8 words per lane (4 per net)
-    // (a wave past the batch writes its bits into block 0's record of this
-    // layer ... never: net_tape stores them only when `bp` is non-null)
-    uint32_t* bp = live ? tbits + ((int64_t)l * nwb + row0 / kRows) * 512 + lane * 8 : nullptr;
+    uint32_t* bp = tbits + ((int64_t)l * nwb + row0 / kRows) * 512 + lane * 8;
     if constexpr (NETS == 2) {  // forward stream: t-net (tape net 1), then s-net (net 0)
       net_tape<G, TP, 2, 0, 1>(ring, wl, wn, bl, X, et, tp, bp, lane);
       EpAffineTape<XT, CT, TT, TP::So> ea{X, Tv, ld, tp};
@@ -992,10 +912,6 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_wtrain16_fwd(
     }
     pad_steps<G, NETS, P>(ring, wl, wn, std::make_integer_sequence<int, LSP - NETS * G::steps()>{});
     relayout<G>(st, qs, S, qtab + l * D, X, lane);
-  }
-  if constexpr (G::kLdsA) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA outlives the block
-    if (!live) return;
   }
 
   put_state<G>(st, S, X, lane);
@@ -1049,7 +965,6 @@ struct EpMaskTape {
 
 template <int OFF, int T>
 __device__ __forceinline__ void g_tiles(const Rows16& gb, const v4 (&h)[T][2]) {
-  if (!(CNF_W16_TAPE & 4)) return;
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll
@@ -1143,7 +1058,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_wtrain16_bwd(
     const int r = i / D, f = i - r * D;
     st[r * S + f] = r < nrows ? src[i] : 0.f;
   }
-  constexpr int P = ring16(LSP, CNF_W16_PMAX);
+  constexpr int P = ring16(LSP, kPMax);
   float ring[P];
   {
     const float* a0 = WT + (int64_t)(L - 1) * LT + kLaneStride * lane;
@@ -1371,32 +1286,39 @@ const WEntry16* w16find(const Shape& s) {
   return nullptr;
 }
 
-size_t w16_lds(const Shape& s, int rows = kRows) {
-  return (size_t)kWaves * (rows * (s.D | 1) + s.D) * 4;
-}
+size_t w16_lds(const Shape& s) { return (size_t)kWaves * (kRows * (s.D | 1) + s.D) * 4; }
 
 }  // namespace
 
-// per layer: the forward stream and biases (all layers first), then the
-// transposed stream of the reverse sweep (after the L forward records)
-// transposed-stream floats per layer (pads included: G16T::lsp)
+// The wide region, per layer: the forward stream and biases (all layers
+// first), then the transposed stream of the reverse sweep (after the L forward
+// records).
 // forward A-stream floats per layer (pads included: G16::lsp)
 static int64_t w16_la(const WEntry16* e, int nets) {
   const int ls = nets * (e->na / 64);
   return (int64_t)pad_fwd(ls) * 64;
 }
 
+// transposed-stream floats per layer (pads included: G16T::lsp)
 static int64_t w16_lt(const WEntry16* e, int nets) {
   const int ls = nets * (e->nat / 64);
-  return (int64_t)pad_ls(ls, CNF_W16_BWD_P16) * 64;
+  return (int64_t)pad_bwd(ls) * 64;
 }
 
-int64_t wide16_layer_floats(const Shape& s) {
+int64_t wide_layer_floats(const Shape& s) {
   const WEntry16* e = w16find(s);
   return e ? w16_la(e, s.nets) + (int64_t)s.nets * e->nb + w16_lt(e, s.nets) : 0;
 }
 
-int wide16_prepare(const Shape& s, const float* const* params, void* prepared, hipStream_t st) {
+// Final-output forward / inverse of shift-on, non-strict stacks in the table
+// (and their fused training sweeps); every-layer outputs and strict_nan stay on
+// k_tile.
+bool wide_ok(const Shape& s) {
+  return w16find(s) && s.shift && !s.strict && !s.alt_mask && !s.s_tanh &&
+         !(s.options & CNF_OPT_NO_WIDE);
+}
+
+int wide_prepare(const Shape& s, const float* const* params, void* prepared, hipStream_t st) {
   const WEntry16* e = w16find(s);
   if (!e) return CNF_OK;
   float* region = reinterpret_cast<float*>(static_cast<char*>(prepared) + idx_bytes(s)) +
@@ -1455,8 +1377,8 @@ int wide16_prepare(const Shape& s, const float* const* params, void* prepared, h
   return CNF_OK;
 }
 
-int wide16_run(const Shape& s, const void* prepared, const float* in, float* out, float* ld,
-               int64_t B, bool inverse, hipStream_t st, const float* log_priors) {
+int wide_run(const Shape& s, const void* prepared, const float* in, float* out, float* ld,
+             int64_t B, bool inverse, hipStream_t st, const float* log_priors) {
   const WEntry16* e = w16find(s);
   if (!e) return CNF_ERR_UNSUPPORTED;
   if (log_priors && inverse) return CNF_ERR_UNSUPPORTED;
@@ -1464,11 +1386,10 @@ int wide16_run(const Shape& s, const void* prepared, const float* in, float* out
   const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
   const int32_t* inv_q = fwd_q + s.L * s.D;
   const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.wide_region;
-  const int64_t rows_per_block = (int64_t)kRunRows * kWaves;
+  const int64_t rows_per_block = (int64_t)kRows * kWaves;
   const dim3 grid((unsigned)((B + rows_per_block - 1) / rows_per_block)), block(64 * kWaves);
   WFn fn = e->fn[s.nets - 1][log_priors ? 2 : (inverse ? 1 : 0)];
-  const size_t lds = CNF_W16_LDSA ? (size_t)(cdiv(kWaves * (kRunRows * (s.D | 1) + s.D), 64) * 64 + 2 * kAC * 64) * 4
-                                  : w16_lds(s, kRunRows);
+  const size_t lds = (size_t)(state_floats(s.D) + 2 * kAC * 64) * 4;  // state areas, two A stages
   hipLaunchKernelGGL(fn, grid, block, lds, st, W, inverse ? inv_q : fwd_q, in, out, ld, B,
                      s.L, log_priors);
   hipError_t err = hipGetLastError();
@@ -1507,10 +1428,7 @@ int wide16_train_forward(const Shape& s, const void* prepared, const float* x, f
     sa.grad_scale = seed->grad_scale;
     sa.kind = seed->kind;
   }
-  const size_t lds = CNF_W16_TRAIN_LDSA && kRunRows == kRows
-                         ? (size_t)(cdiv(kWaves * (kRows * (s.D | 1) + s.D), 64) * 64 + 2 * kAC * 64) * 4
-                         : w16_lds(s);
-  hipLaunchKernelGGL(e->tfwd[s.nets - 1], grid, block, lds, st, W, fwd_q, x, zst, ld, tape,
+  hipLaunchKernelGGL(e->tfwd[s.nets - 1], grid, block, w16_lds(s), st, W, fwd_q, x, zst, ld, tape,
                      tbits, B, s.L, Cp, Dp, sa);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {

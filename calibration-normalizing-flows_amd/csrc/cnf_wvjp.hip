@@ -321,7 +321,8 @@ struct DwJob {
   const float* H;
   int64_t ldg, ldh;
   int64_t woff, boff;  // float offsets of W[0][in_off] and b[0] in the layer record
-  int wld, N, K, tiles_c;  // tiles_c: 32-column tiles of [H | 1] (K + 1 columns)
+  int wld, N, K, tiles_c;  // tiles_c: 32-column tiles of [H | 1] (K + 1 columns; no kernel
+                           // reads it now, it keeps the argument block's layout)
   int cstep;           // +1, or -1 when the kernel's input columns run reversed (legacy)
   int rrev;            // output rows reversed (legacy): row n is parameter row N_full-1-n
   int nfull;
@@ -335,143 +336,21 @@ struct DwArgs {
   int64_t M, rows, PS;
 };
 
-// CNF_WDW16 (default 1): the layer-at-a-time weight gradients on k_wdw16's
-// 16x16x4 tiles; 0 compiles and runs k_wdw's 32x32x2 predecessor instead
-// (A/B builds only: make ab ABSRC=cnf_wvjp DEFS=-DCNF_WDW16=0)
-#ifndef CNF_WDW16
-#define CNF_WDW16 1
-#endif
-#if !CNF_WDW16
-constexpr int kDwCT = 4;  // column tiles per wave (128 columns)
-
-__global__ __launch_bounds__(256, 3) void k_wdw(DwArgs da) {
-  // the job's fields once, into scalar registers (a reference into the
-  // argument block indexed by blockIdx.y reloads every field at every use)
-  const DwJob j = da.job[blockIdx.y];
-  const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nsub = (j.N + 31) >> 5, ncg = (j.tiles_c + kDwCT - 1) / kDwCT;
-  const int gn = (int)blockIdx.z / ncg, cg = (int)blockIdx.z % ncg;
-  const int ns = gn * 4 + w;
-  if (gn * 4 >= nsub || ns >= nsub) return;  // no __syncthreads below: waves may leave
-  const int nct = min(kDwCT, j.tiles_c - cg * kDwCT);
-  const int n0 = ns * 32, c0 = cg * 32 * kDwCT;
-  const int64_t r0 = (int64_t)blockIdx.x * da.rows;
-  const int64_t r1 = min(da.M, r0 + da.rows);
-  if (r0 >= r1) return;
-  // operand addresses: buffer loads from a wave-uniform descriptor based at
-  // the chunk's first row (scalar arithmetic), a per-lane 32-bit byte offset
-  // fixed for the whole launch (row h of the pair, column n0 + i / c0 + 32c +
-  // i, clamped in-row) and a scalar offset per row pair -- no per-load vector
-  // address arithmetic
-  const int ldg = (int)j.ldg, ldh = (int)j.ldh;
-  const int goff = (h * ldg + min(n0 + i, j.N - 1)) * 4;
-  int hoff[kDwCT];
-#pragma unroll
-  for (int c = 0; c < kDwCT; ++c) hoff[c] = (h * ldh + min(c0 + 32 * c + i, ldh - 1)) * 4;
-  // 16-row chunks (8 MFMA k-steps) in two operand sets used in turn: the next
-  // chunk's loads are issued before this chunk's MFMAs without register copies
-  constexpr int KS = 8;
-  auto load = [&](int64_t mr, float (&a)[KS], float (&b)[kDwCT][KS]) {
-    const auto gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(j.G + mr * ldg), 0,
-                                                      0x7fffffff, 0x00020000);
-    const auto hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(j.H + mr * ldh), 0,
-                                                      0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-      a[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(gr, goff, 2 * s * ldg * 4, 0));
-#pragma unroll
-    for (int c = 0; c < kDwCT; ++c)
-      if (c < nct) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-          b[c][s] = __builtin_bit_cast(
-              float, __builtin_amdgcn_raw_buffer_load_b32(hr, hoff[c], 2 * s * ldh * 4, 0));
-      }
-  };
-  auto mfmas = [&](f16v (&acc)[kDwCT], const float* a, const float (*b)[KS], int ks) {
-#pragma unroll
-    for (int c = 0; c < kDwCT; ++c)
-      if (c < nct) {
-#pragma unroll
-        for (int s = 0; s < ks; ++s)
-          acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[c][s], acc[c], 0, 0, 0);
-      }
-  };
-  f16v acc[kDwCT];
-#pragma unroll
-  for (int c = 0; c < kDwCT; ++c) acc[c] = f16v{};
-  const int64_t rfull = r0 + (r1 - r0) / 16 * 16;  // rows in whole chunks
-  if (rfull > r0) {
-    float a0[KS], b0[kDwCT][KS], a1[KS], b1[kDwCT][KS];
-    load(r0, a0, b0);
-    for (int64_t mr = r0;; mr += 32) {
-      const bool more1 = mr + 16 < rfull;
-      if (more1) load(mr + 16, a1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(acc, a0, b0, KS);
-      if (!more1) break;
-      const bool more2 = mr + 32 < rfull;
-      if (more2) load(mr + 32, a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(acc, a1, b1, KS);
-      if (!more2) break;
-    }
-  }
-  if (rfull < r1) {  // the batch's ragged end: rows past r1 contribute zero
-    float a[KS], b[kDwCT][KS];
-    const float* G = j.G;
-    const float* H = j.H;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int64_t row = rfull + 2 * s + h;
-      const bool ok = row < r1;
-      const int64_t rr = ok ? row : r1 - 1;
-      a[s] = ok ? G[rr * ldg + min(n0 + i, j.N - 1)] : 0.f;
-#pragma unroll
-      for (int c = 0; c < kDwCT; ++c) b[c][s] = H[rr * ldh + min(c0 + 32 * c + i, ldh - 1)];
-    }
-    mfmas(acc, a, b, KS);
-  }
-  float* out = da.partials + (int64_t)blockIdx.x * da.PS;
-#pragma unroll
-  for (int c = 0; c < kDwCT; ++c) {
-    const int k = c0 + c * 32 + i;
-    if (c >= nct || k > j.K) continue;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int nn = n0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-      if (nn >= j.N) continue;
-      const int pr = j.rrev ? j.nfull - 1 - nn : nn;  // parameter row
-      if (k < j.K) out[j.woff + (int64_t)pr * j.wld + (int64_t)j.cstep * k] = acc[c][q];
-      else out[j.boff + pr] = acc[c][q];
-    }
-  }
-}
-
-#endif  // !CNF_WDW16
-
-// The same weight gradients on v_mfma_f32_16x16x4f32 tiles (the same 64
-// FLOP/clk/SIMD as 32x32x2): a wave still owns 32 output rows, and up to 112
+// The layer-at-a-time weight gradients on v_mfma_f32_16x16x4f32 tiles (the
+// same 64 FLOP/clk/SIMD as 32x32x2): a wave owns 32 output rows, and up to 112
 // columns, as 16 x 16 tiles, so a job's padding is to the next 16 instead of 32 --
 // N = 100 needs 7 row tiles (112) instead of 4 x 32 (128), the 101 columns
 // of [H | 1] 7 column tiles (112) instead of 128: the (100, 101) job issues
 // 49 tiles' MFMAs instead of 64, a cfg4 layer 18 % fewer in all.  Operand
 // loads per 16 rows are unchanged (K-step s: lane (i, q) reads G[row 4s + q]
 // [n + i] and H[row 4s + q][c + i], 64 contiguous bytes per quarter-wave).
-#ifndef CNF_DW16_CT
-#define CNF_DW16_CT 7
-#endif
 // 16-column tiles per wave (7: 112 columns, [H | 1] of a 100-wide layer in one
 // block; 4: two blocks of 64 + 48 columns, half the accumulators, four waves
 // per SIMD)
-constexpr int kDw16CT = CNF_DW16_CT;
-#ifndef CNF_DW16_KS
-#define CNF_DW16_KS 4
-#endif
+constexpr int kDw16CT = 7;
 // MFMA k-steps (of 4 rows) per operand set: 4 (16-row chunks, 149 VGPRs, 3
 // waves per SIMD) or 2 (8-row chunks, 4 waves per SIMD)
-constexpr int kDw16KS = CNF_DW16_KS;
+constexpr int kDw16KS = 4;
 
 // unit of slot c in a 16-slot tile (cnf_wide16.hip's q-major fill; an involution)
 __device__ __forceinline__ int slot_unit(int c) {
@@ -681,11 +560,6 @@ __device__ __forceinline__ void wdwg_chunks(const DwJob& j, float* sm, int w, in
 // one (each block's fourth SIMD half idle), a 1-row-tile job all its work to
 // wave 0.  A wave reads the operand tiles its pairs touch (unused reads are
 // dropped by the compiler) and writes its own cells.
-#ifndef CNF_WDWG_RR
-#define CNF_WDWG_RR 1
-#endif
-// A/B timing only (wrong results): 1 = no MFMAs, 2 = no operand DMA (the
-// MFMAs run on whatever the LDS stages hold)
 template <int NTG, int NTH, int W>
 __device__ __forceinline__ void wdwg_rr(const DwJob& j, const DwArgs& da, float* sm, int lane,
                                         int64_t r0, int nch) {
@@ -749,11 +623,11 @@ __device__ __forceinline__ void wdwg_rr(const DwJob& j, const DwArgs& da, float*
 
 // the (G tiles, H tiles) classes with an instantiation: the weight gradients
 // of k_wide16's table (cfg4: (7, 4), (7, 7), (4, 7))
-#define CNF_WDWG_CLASSES(X) X(7, 4) X(7, 7) X(4, 7) X(4, 4) X(4, 2) X(4, 5) X(1, 5)
+#define CNF_DWG_CLASSES(X) X(7, 4) X(7, 7) X(4, 7) X(4, 4) X(4, 2) X(4, 5) X(1, 5)
 inline bool wdwg_class_ok(int ntg, int nth) {
-#define CNF_WDWG_OK(A, B) if (ntg == A && nth == B) return true;
-  CNF_WDWG_CLASSES(CNF_WDWG_OK)
-#undef CNF_WDWG_OK
+#define CNF_DWG_OK(A, B) if (ntg == A && nth == B) return true;
+  CNF_DWG_CLASSES(CNF_DWG_OK)
+#undef CNF_DWG_OK
   return false;
 }
 
@@ -775,9 +649,9 @@ __global__ __launch_bounds__(256, 2) void k_wdw16g(DwArgs da) {
     for (int c = 0; c < 8; ++c) acc[t][c] = f4{};
   // every wave runs the chunk loop (it copies its share and meets the
   // barriers) whatever its row-tile count
-#define CNF_WDWG_RUN(A, B)                                                    \
+#define CNF_DWG_RUN(A, B)                                                     \
   if (ntg == A && nth == B) {                                                 \
-    if (CNF_WDWG_RR && A % 4 != 0) {                                          \
+    if (A % 4 != 0) {                                                         \
       if (w == 0) wdwg_rr<A, B, 0>(j, da, sm, lane, r0, nch);                 \
       else if (w == 1) wdwg_rr<A, B, 1>(j, da, sm, lane, r0, nch);            \
       else if (w == 2) wdwg_rr<A, B, 2>(j, da, sm, lane, r0, nch);            \
@@ -788,8 +662,8 @@ __global__ __launch_bounds__(256, 2) void k_wdw16g(DwArgs da) {
     else if (nr == 1) wdwg_chunks<A, B, 1>(j, sm, w, lane, r0, nch, acc);      \
     else wdwg_chunks<A, B, 0>(j, sm, w, lane, r0, nch, acc);                   \
   } else
-  CNF_WDWG_CLASSES(CNF_WDWG_RUN) {}
-#undef CNF_WDWG_RUN
+  CNF_DWG_CLASSES(CNF_DWG_RUN) {}
+#undef CNF_DWG_RUN
   // lane (i, kq), register q of tile (t, c): dW row slot 16 (w + 4t) + 4 kq + q,
   // column slot 16 c + i, each mapped to its unit
   float* out = da.partials + (int64_t)blockIdx.x * da.PS;
@@ -810,10 +684,6 @@ __global__ __launch_bounds__(256, 2) void k_wdw16g(DwArgs da) {
     }
   }
 }
-
-#ifndef CNF_WDW16G
-#define CNF_WDW16G 1  // A/B: 0 runs the fused sweeps' weight gradients on k_wdw16
-#endif
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -1416,12 +1286,10 @@ struct Plan16 {
   int64_t tape, tbits, zst, ld, gld, g0, gbuf, seed, part, total, nkb, rows_kb, nseed;
 };
 constexpr double kTapeMaxBytes = 96.0 * (1ull << 30);  // beyond: the layer-at-a-time path
-#ifndef CNF_WDWG_NKB
-#define CNF_WDWG_NKB 256
-#endif
+constexpr int kWdwgNkb = 256;  // k_wdw16g's row blocks (plan16)
 
 bool plan16(const Shape& s, int64_t B, WTrain16Layout* lay, Plan16* p) {
-  if (!wide16_train_ok(s) || wide16_train_layout(s, lay) != CNF_OK) return false;
+  if (!wide_ok(s) || wide16_train_layout(s, lay) != CNF_OK) return false;
   const int64_t Bn = B > 0 ? B : 1;
   const int64_t Bp = wide16_blocks(Bn) * 32;  // whole 32-row blocks (wave-tiled arrays)
   if ((double)s.L * Bp * (lay->RW + lay->GW) * 4 > kTapeMaxBytes) return false;
@@ -1441,11 +1309,11 @@ bool plan16(const Shape& s, int64_t B, WTrain16Layout* lay, Plan16* p) {
   p->gbuf = take((int64_t)s.L * Bp * lay->GW);
   p->nseed = std::min<int64_t>(4096, (Bn + 15) / 16);  // k_wseed's blocks (generic seeds)
   p->seed = take(std::max<int64_t>(p->nseed, wide16_blocks(Bn)) * 4);  // or one record per wave
-  // k_wdw16g's row blocks: CNF_WDWG_NKB of them (each one record of dW
+  // k_wdw16g's row blocks: kWdwgNkb of them (each one record of dW
   // partials that the fixed-order reduction reads back).  At cfg4 (2^18 rows)
   // 256 measured 255 us per layer; 128 / 171 / 512 blocks 300 / 293 / 278 us
   // (fewer blocks: a ragged last round of the 2-per-CU grid; more: partials)
-  int64_t rows = (Bn + CNF_WDWG_NKB - 1) / CNF_WDWG_NKB;
+  int64_t rows = (Bn + kWdwgNkb - 1) / kWdwgNkb;
   rows = std::max<int64_t>(256, (rows + 31) / 32 * 32);
   p->rows_kb = rows;
   p->nkb = (Bn + rows - 1) / rows;
@@ -1521,7 +1389,7 @@ int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const
         max_subs = std::max(max_subs, ((j.N + 127) / 128) * ncg);
       }
     int maxtpc = 0;
-    bool gok = CNF_WDW16G;
+    bool gok = true;  // every job in a k_wdw16g class, else k_wdw16
     for (int q = 0; q < jobs; ++q) {
       const int ng = (da.job[q].gcl >> 4) + 1, nh = (da.job[q].hcl >> 4) + 1;
       gok = gok && wdwg_class_ok(ng, nh);
@@ -1715,19 +1583,11 @@ struct Runner {
         j.gcl = j.N - 1;
         j.hcl = (int)j.ldh - 1;
         j.slot = 0;
-#if CNF_WDW16
         const int ncg = ((j.K + 1 + 15) / 16 + kDw16CT - 1) / kDw16CT;
-#else
-        const int ncg = (j.tiles_c + kDwCT - 1) / kDwCT;
-#endif
         max_subs = std::max(max_subs, ((j.N + 127) / 128) * ncg);
       }
     }
-#if CNF_WDW16
     hipLaunchKernelGGL(k_wdw16,
-#else
-    hipLaunchKernelGGL(k_wdw,
-#endif
                        dim3((unsigned)p.nkb, (unsigned)jobs, (unsigned)max_subs), dim3(256), 0, st,
                        da);
     reduce_partials(part, (int)p.nkb, (int)PS, (int)PL, grads_layer, nullptr, st);

@@ -163,6 +163,107 @@ def test_wide_training_workspace_plans():
     assert st == 0 and ragged > L * (B + 32) * (640 + 576) * 4
 
 
+# (dim, L, hidden, scale, strict_nan, options) -> kernel family, prepared bytes,
+# cnf_vjp_workspace_bytes and cnf_vjp_inverse_workspace_bytes at B = 1, 32, 33
+# (either side of the whole-32-row-block rule).  Recorded from the build of the
+# last commit that still carried the 32x32x2 wide family and the A/B switches;
+# literals, never computed by the library under test.
+_NW = _lib.OPT_NO_WIDE
+HOST_SIZING = [
+    ((100, 2, [100, 100], 1, 0, 0), 'mfma-wide', 1624512, (559616, 585728, 902144),
+     (253440, 514560, 524800)),
+    ((100, 2, [100, 100], 1, 0, _NW), 'mfma-tile', 1624512, (253440, 514560, 524800),
+     (253440, 514560, 524800)),
+    ((100, 2, [100, 100], 0, 0, 0), 'mfma-wide', 821472, (291072, 317184, 486144),
+     (128512, 292096, 298496)),
+    ((100, 2, [100, 100], 0, 0, _NW), 'mfma-tile', 821472, (128512, 292096, 298496),
+     (128512, 292096, 298496)),
+    ((100, 12, [100, 100], 1, 0, 0), 'mfma-wide', 9744768, (2136576, 2162688, 4056064),
+     (283392, 1333760, 1373952)),
+    ((100, 12, [100, 100], 1, 0, _NW), 'mfma-tile', 9744768, (283392, 1333760, 1373952),
+     (283392, 1333760, 1373952)),
+    ((100, 12, [100, 100], 0, 0, 0), 'mfma-wide', 4926528, (1130752, 1156864, 2165504),
+     (145664, 773376, 796928)),
+    ((100, 12, [100, 100], 0, 0, _NW), 'mfma-tile', 4926528, (145664, 773376, 796928),
+     (145664, 773376, 796928)),
+    ((100, 2, [100], 1, 0, 0), 'mfma-wide', 919680, (364288, 390400, 592128),
+     (169728, 354048, 361216)),
+    ((100, 2, [100], 1, 0, _NW), 'mfma-tile', 919680, (169728, 354048, 361216),
+     (169728, 354048, 361216)),
+    ((100, 2, [100], 0, 0, 0), 'mfma-wide', 460864, (193280, 219392, 331008),
+     (86528, 211712, 216576)),
+    ((100, 2, [100], 0, 0, _NW), 'mfma-tile', 460864, (86528, 211712, 216576),
+     (86528, 211712, 216576)),
+    ((100, 12, [100], 1, 0, 0), 'mfma-wide', 5515776, (1367808, 1393920, 2599168),
+     (189440, 907008, 933888)),
+    ((100, 12, [100], 1, 0, _NW), 'mfma-tile', 5515776, (189440, 907008, 933888),
+     (189440, 907008, 933888)),
+    ((100, 12, [100], 0, 0, 0), 'mfma-wide', 2762880, (746240, 772352, 1436928),
+     (98560, 559872, 576768)),
+    ((100, 12, [100], 0, 0, _NW), 'mfma-tile', 2762880, (98560, 559872, 576768),
+     (98560, 559872, 576768)),
+    ((100, 2, [], 1, 0, 0), 'mfma-wide', 341824, (168704, 194816, 281856),
+     (85760, 193280, 197376)),
+    ((100, 2, [], 1, 0, _NW), 'mfma-tile', 341824, (85760, 193280, 197376),
+     (85760, 193280, 197376)),
+    ((100, 2, [], 0, 0, 0), 'mfma-wide', 176032, (95488, 121600, 175872),
+     (44544, 131328, 134656)),
+    ((100, 2, [], 0, 0, _NW), 'mfma-tile', 176032, (44544, 131328, 134656),
+     (44544, 131328, 134656)),
+    ((100, 12, [], 1, 0, 0), 'mfma-wide', 2048640, (598784, 624896, 1142016),
+     (95232, 480000, 493568)),
+    ((100, 12, [], 1, 0, _NW), 'mfma-tile', 2048640, (95232, 480000, 493568),
+     (95232, 480000, 493568)),
+    ((100, 12, [], 0, 0, 0), 'mfma-wide', 1053888, (361728, 387840, 708352),
+     (51456, 346368, 356608)),
+    ((100, 12, [], 0, 0, _NW), 'mfma-tile', 1053888, (51456, 346368, 356608),
+     (51456, 346368, 356608)),
+    ((32, 2, [64, 64], 1, 0, 0), 'mfma-wide', 434176, (244224, 252928, 429568),
+     (75264, 209920, 217600)),
+    ((32, 2, [64, 64], 1, 0, _NW), 'mfma-tile', 434176, (75264, 209920, 217600),
+     (75264, 209920, 217600)),
+    ((32, 2, [64, 64], 0, 0, 0), 'mfma-wide', 217600, (129024, 137728, 232448),
+     (38656, 117248, 121600)),
+    ((32, 2, [64, 64], 0, 0, _NW), 'mfma-tile', 217600, (38656, 117248, 121600),
+     (38656, 117248, 121600)),
+    ((32, 12, [64, 64], 1, 0, 0), 'mfma-wide', 2602496, (1124864, 1133568, 2190848),
+     (102656, 670720, 705792)),
+    ((32, 12, [64, 64], 1, 0, _NW), 'mfma-tile', 2602496, (102656, 670720, 705792),
+     (102656, 670720, 705792)),
+    ((32, 12, [64, 64], 0, 0, 0), 'mfma-wide', 1303040, (600064, 608768, 1174528),
+     (53248, 373248, 392192)),
+    ((32, 12, [64, 64], 0, 0, _NW), 'mfma-tile', 1303040, (53248, 373248, 392192),
+     (53248, 373248, 392192)),
+    ((100, 12, [100, 100], 1, 1, 0), 'mfma-tile', 10210176, (292608, 1573376, 1622784),
+     (292608, 1573376, 1622784)),
+    ((10, 3, [4, 6, 3], 1, 0, 0), 'mfma-tile', 14504, (11008, 45568, 54528),
+     (11008, 45568, 54528)),
+]
+
+
+def test_wide_host_sizing_is_pinned():
+    """Kernel family, prepared-blob size and both reverse-mode workspace plans
+    of every shape in the wide table (and one outside it) are the recorded ones:
+    the host-side half of the wide family that no ISA listing covers."""
+    lib = _lib.lib()
+    assert len(HOST_SIZING) == 4 * 2 * 2 * 2 + 2
+
+    def size(fn, d, *args):
+        n = ctypes.c_size_t()
+        assert fn(ctypes.byref(d), *args, ctypes.byref(n)) == 0
+        return n.value
+
+    for (dim, L, hidden, scale, strict, options), name, prepared, vjp, inv in HOST_SIZING:
+        d = _lib.make_desc(dim, L, hidden, scale=scale, strict_nan=strict, options=options)
+        case = (dim, L, hidden, scale, strict, options)
+        assert lib.cnf_kernel_name(ctypes.byref(d)).decode() == name, case
+        assert size(lib.cnf_prepared_bytes, d) == prepared, case
+        for B, want_v, want_i in zip((1, 32, 33), vjp, inv):
+            assert size(lib.cnf_vjp_workspace_bytes, d, ctypes.c_int64(B)) == want_v, (case, B)
+            assert size(lib.cnf_vjp_inverse_workspace_bytes, d,
+                        ctypes.c_int64(B)) == want_i, (case, B)
+
+
 def test_guard_argument_validation_without_gpu():
     """cnf_guard_nonfinite rejects bad arguments before any launch."""
     import ctypes
