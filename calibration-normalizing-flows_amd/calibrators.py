@@ -8,6 +8,9 @@ step is ONE fused native launch (forward + calibrator loss + reverse mode,
 cnf_loss_vjp) followed by the optimizer step, and the per-epoch evaluation is
 ONE fused forward + loss launch (cnf_forward_loss); history entries stay
 device tensors, as in the reference, so no step synchronises the host.
+A flow made of PlanarLayers (flows._factory.PlanarFlow) trains the same way on
+its own kernels: cnf_planar_loss_vjp per batch, then torch's own Adam step, and
+cnf_planar_forward_loss per evaluation batch.
 Any other flow (or a CPU device) runs the reference's own torch loop.
 
 The scaling baselines -- TempScalingCalibrator, MLRCalibrator,
@@ -384,6 +387,33 @@ def _native_stack(flow, dev, need_vjp=True):
     return stack if st == 0 else None
 
 
+def _planar_stack(flow, dev):
+    """The fused PlanarStack behind `flow`, or None when the flow is not an
+    all-planar Flow with fp32 parameters on the ROCm device `dev`, the shape is
+    outside the kernels' envelope, or CNF_PLANAR_NATIVE=0."""
+    if torch.device(dev).type != "cuda":
+        return None
+    try:
+        from flows import flows as F
+        from cnf_hip import _lib
+        from cnf_hip.planar import PlanarStack
+    except ImportError:
+        return None
+    if not F.PLANAR_NATIVE or not isinstance(flow, F.Flow):
+        return None
+    layers = list(flow.layers)
+    if not layers or not all(isinstance(l, F.PlanarLayer) for l in layers):
+        return None
+    ps = [p for l in layers for p in (l.w, l.u, l.b)]
+    if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
+        return None
+    if not PlanarStack.compatible(layers, ps[0].device):
+        return None
+    if not (1 <= layers[0].w.numel() <= _lib.MAX_DIM and len(layers) <= _lib.PLANAR_MAX_LAYERS):
+        return None
+    return flow._planar_stack()
+
+
 def _loader_order(n):
     """The row order of one pass of DataLoader(TensorDataset(...), batch_size,
     shuffle=True) (calibrators.py:274-275) with torch's global CPU RNG in the
@@ -509,6 +539,10 @@ class TorchFlowCalibrator(Calibrator):
             # that the calibrator's `dev`, which need not be the current GPU
             with torch.cuda.device(logits.device):
                 history = self._fit_native(stack, logits, target, epochs, batch_size)
+        elif _planar_stack(self.flow, self.dev) is not None:
+            with torch.cuda.device(logits.device):
+                history = self._fit_planar(_planar_stack(self.flow, self.dev), logits, target,
+                                           epochs, batch_size)
         else:
             history = self._fit_torch(logits, target, epochs, batch_size)
         self.flow.cpu()
@@ -584,6 +618,42 @@ class TorchFlowCalibrator(Calibrator):
             e += 1
         adam.store_into(self.optimizer)
         stack.invalidate()  # drop blobs / workspaces captured into a graph pool
+        hist = terms_all[:epochs] / N
+        return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
+                'log_det': list(hist[:, 2].unbind(0))}
+
+    def _fit_planar(self, stack, logits, target, epochs, batch_size):
+        """The same schedule for an all-planar flow: per training batch one
+        cnf_planar_loss_vjp launch whose flat gradient is viewed into each
+        parameter's .grad, then torch's own Adam step (the optimizer state
+        stays torch's); per evaluation batch one cnf_planar_forward_loss
+        launch.  Every pass draws its order as the reference's
+        DataLoader(shuffle=True) does (_loader_order), and the history keeps
+        the last batch's sums over N (calibrators.py:274-317)."""
+        N = logits.shape[0]
+        bs = max(1, int(batch_size))
+        dev = logits.device
+        params = stack.param_tensors()
+        flat = torch.empty(stack.param_count(), dtype=torch.float32, device=dev)
+        views = stack.split(flat)
+        terms_all = torch.empty(max(epochs, 1), 3, dtype=torch.float32, device=dev)
+        for e in range(epochs):
+            order = _loader_order(N).to(dev, non_blocking=True)
+            xs, ys = logits.index_select(0, order), target.index_select(0, order)
+            for s in range(0, N, bs):
+                xb, yb = xs[s:s + bs], ys[s:s + bs]
+                stack.loss_and_grads(xb, yb, grad_scale=1.0 / xb.shape[0], grads_out=flat)
+                for p, g in zip(params, views):
+                    p.grad = g
+                self.optimizer.step()
+            order = _loader_order(N).to(dev, non_blocking=True)
+            xe, ye = logits.index_select(0, order), target.index_select(0, order)
+            for s in range(0, N, bs):
+                last = s + bs >= N
+                stack.forward_loss(xe[s:s + bs], ye[s:s + bs],
+                                   terms_out=terms_all[e] if last else None)
+        for p in params:
+            p.grad = None
         hist = terms_all[:epochs] / N
         return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
                 'log_det': list(hist[:, 2].unbind(0))}

@@ -8,7 +8,7 @@ from `flows.realNVP_torch` / `flows.nice_torch`, modules absent from the
 reference repo; their defaults here follow code-old/realNVP.py:46-52
 (layers=4, hidden_size=[dim]) and are otherwise unpinned.
 """
-from .flows import Flow, NvpCouplingLayer
+from .flows import Flow, NvpCouplingLayer, PlanarLayer
 
 
 class CouplingFlow(Flow):
@@ -29,6 +29,22 @@ class CouplingFlow(Flow):
 
     def backward(self, z):
         return self.inverse_transform(z)
+
+    def forward_all(self, x):
+        """The reference Flow.forward: (zs list, cum_log_det)."""
+        return Flow.forward(self, x)
+
+
+class PlanarFlow(Flow):
+    """A Flow of PlanarLayers whose call returns (z_final, log_det); layers=10
+    as get_Planarmodel of the reference's calibration notebooks."""
+
+    def __init__(self, dim, layers=10, **kwargs):
+        super().__init__([PlanarLayer(dim) for _ in range(layers)])
+        self.dim = dim
+
+    def forward(self, x):
+        return self.transform(x)
 
     def forward_all(self, x):
         """The reference Flow.forward: (zs list, cum_log_det)."""

@@ -4,7 +4,9 @@ Same classes, constructor arguments, attributes, state_dict keys and return
 conventions as the reference (SergioAlvarezB/calibration-normalizing-flows,
 flows/flows.py), so `from flows.flows import Flow, NvpCouplingLayer` works
 unchanged.  On a ROCm device a Flow made of NvpCouplingLayers runs as ONE fused
-HIP launch per call (libcnf_hip.so, include/cnf.h):
+HIP launch per call (libcnf_hip.so, include/cnf.h), and so does a Flow made of
+PlanarLayers (cnf_planar_*; forward only, the planar flow has no tractable
+inverse):
 
   Flow.forward(x)  -> (zs, cum_log_det)   fused cnf_forward, zs = views of one
                                            [L, B, D] buffer       (flows.py:17-25)
@@ -15,8 +17,9 @@ HIP launch per call (libcnf_hip.so, include/cnf.h):
 from torch autograd, which calls the native VJP kernel.
 
 Host tensors (CPU) run the same math with torch ops, as the reference does.
-Layers the native engine does not cover (AffineConstantLayer, PlanarLayer,
-RadialLayer -- out of the hot-path scope) also run as torch ops.
+Layers the native engine does not cover (AffineConstantLayer, RadialLayer --
+out of the hot-path scope) and mixed stacks run as torch ops, layer
+by layer.  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops as well.
 """
 import os
 import warnings
@@ -35,6 +38,10 @@ STRICT_NAN = os.environ.get("CNF_STRICT_NAN", "0") == "1"
 # Raise instead of running torch ops when a ROCm tensor cannot take the
 # native path (unsupported shape or activation).
 STRICT_NATIVE = os.environ.get("CNF_STRICT_NATIVE", "0") == "1"
+
+# CNF_PLANAR_NATIVE=0: planar flows on a ROCm device stay on the torch ops
+# (the baseline of tools/planar_bench.py).
+PLANAR_NATIVE = os.environ.get("CNF_PLANAR_NATIVE", "1") != "0"
 
 _warned = set()
 
@@ -74,6 +81,38 @@ def _native_eligible(layers, x):
     return True
 
 
+def _planar_eligible(layers, x):
+    """True when these layers can run as one fused planar stack on x."""
+    if not PLANAR_NATIVE or not (isinstance(x, torch.Tensor) and x.is_cuda):
+        return False
+    if x.dtype != torch.float32 or x.dim() != 2:
+        return False
+    if not layers or not all(isinstance(ly, PlanarLayer) for ly in layers):
+        return False
+    from cnf_hip.planar import PlanarStack
+    # PlanarLayer(params=...) tensors that sit on another device fall through
+    # to the torch ops, which fail there as the reference does
+    if not PlanarStack.compatible(layers, x.device):
+        return False
+    return x.shape[1] == layers[0].w.numel()
+
+
+def _planar_run(stack, x, want_all):
+    """(zs list | final z, log-det) of a PlanarStack, or None when the shape is
+    outside the kernels' envelope."""
+    from cnf_hip._lib import UnsupportedShape
+    try:
+        if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
+            out, ld = stack.forward_autograd(x, want_all=want_all)
+        else:
+            fin, ld, allt = stack.run(x, want_all=want_all)
+            out = allt if want_all else fin
+        return (list(out.unbind(0)) if want_all else out), _squeeze_ld(ld)
+    except UnsupportedShape as e:
+        _not_native(str(e))
+        return None
+
+
 def _squeeze_ld(ld):
     # torch.sum(..., dim=1).squeeze(): 0-d for a single row (flows/flows.py:109)
     return ld.squeeze()
@@ -93,12 +132,16 @@ class Flow(nn.Module):
         self.native_options = int(kwargs.get("native_options", 0))
         self._stack = None
         self._stack_key = None
+        self._pstack = None
+        self._pstack_key = None
 
     def __getstate__(self):
         # the native binding (ctypes descriptor, device blobs) is rebuilt lazily
         st = self.__dict__.copy()
         st["_stack"] = None
         st["_stack_key"] = None
+        st["_pstack"] = None
+        st["_pstack_key"] = None
         return st
 
     # -- native plumbing --------------------------------------------------
@@ -111,12 +154,22 @@ class Flow(nn.Module):
             self._stack_key = key
         return self._stack
 
+    def _planar_stack(self):
+        key = tuple((id(ly), id(ly.w), id(ly.u), id(ly.b)) for ly in self.layers)
+        if getattr(self, "_pstack", None) is None or self._pstack_key != key:
+            from cnf_hip.planar import PlanarStack
+            self._pstack = PlanarStack(list(self.layers))
+            self._pstack_key = key
+        return self._pstack
+
     def invalidate_native(self):
         """Drop the native binding's prepared weights.  Needed only after writes
         that bypass torch's version counters (`p.data.copy_(...)`); optimizer
         steps, `load_state_dict` and in-place ops are tracked automatically."""
         self._stack = None
         self._stack_key = None
+        self._pstack = None
+        self._pstack_key = None
         for ly in self.layers:
             if isinstance(ly, NvpCouplingLayer):
                 ly._stack = None
@@ -126,7 +179,11 @@ class Flow(nn.Module):
 
     def _try_native(self, x, inverse, want_all=True):
         """(zs list | final z, log-det) from one fused launch, or None."""
-        if not _native_eligible(list(self.layers), x):
+        layers = list(self.layers)
+        if not inverse and layers and isinstance(layers[0], PlanarLayer) \
+                and _planar_eligible(layers, x):
+            return _planar_run(self._planar_stack(), x, want_all)
+        if not _native_eligible(layers, x):
             return None
         from cnf_hip._lib import UnsupportedShape
         stack = self._native_stack()
@@ -304,8 +361,9 @@ class NvpCouplingLayer(nn.Module):
 
 
 class PlanarLayer(nn.Module):
-    """Planar flow (reference flows/flows.py:129-165); non-invertible.
-    Torch ops on every device (outside the coupling hot path)."""
+    """Planar flow (reference flows/flows.py:129-165); non-invertible.  On a
+    ROCm device one fused launch (cnf_planar_forward, L = 1); torch ops on the
+    host."""
 
     def __init__(self, dim=0, params=None):
         super().__init__()
@@ -320,8 +378,27 @@ class PlanarLayer(nn.Module):
             self.u = nn.Parameter(torch.rand(dim))
             self.b = nn.Parameter(torch.rand(1))
         self.invertible = False
+        self._stack = None
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_stack"] = None
+        return st
+
+    def _native(self, x):
+        if not _planar_eligible([self], x):
+            return None
+        st = getattr(self, "_stack", None)
+        if st is None or st.param_tensors()[0] is not self.w or st.param_tensors()[1] is not self.u \
+                or st.param_tensors()[2] is not self.b:
+            from cnf_hip.planar import PlanarStack
+            st = self._stack = PlanarStack([self])
+        return _planar_run(st, x, want_all=False)
 
     def forward(self, x):
+        out = self._native(x)
+        if out is not None:
+            return out
         wtu = torch.dot(self.w, self.u)
         m = -1 + torch.log1p(torch.exp(wtu))   # keeps w.u_hat >= -1
         u_hat = self.u + (m - wtu) * self.w / torch.norm(self.w)

@@ -348,6 +348,73 @@ int cnf_pav_predict(const float* x, int32_t dim, int64_t B, const double* thr_x,
                     const double* thr_y, const int32_t* n_thr, int32_t cap,
                     const double* log_priors, float* probs, void* stream);
 
+/* Planar flows: a Flow of the reference's PlanarLayers (flows/flows.py:129-165;
+ * get_Planarmodel / train_planar of the calibration notebooks).  Per layer,
+ * with parameters w [D], u [D], b [1] (that state_dict order):
+ *   wtu = w.u,  m = -1 + log1p(exp(wtu)),  u_hat = u + ((m - wtu) * w) / ||w||
+ *   h = tanh(x.w + b),  z = x + h * u_hat,  log_det = log|1 + (1 - h^2) (w.u_hat)|
+ * (the division is by the norm, not its square, and ||w|| = 0 gives NaN, as in
+ * the reference; the log-det is -inf where its argument is 0).  All fp32.
+ *   dim       D, 1..CNF_MAX_DIM;  n_layers  L, 1..CNF_PLANAR_MAX_LAYERS
+ *             (< 1: CNF_ERR_DESC; above: CNF_ERR_UNSUPPORTED)
+ *   params    HOST array of 3 * L DEVICE pointers: w, u, b of layer 0, 1, ...
+ *   B         0..2^31 rows (CNF_ERR_BATCH otherwise)
+ *   workspace cnf_planar_workspace_bytes(dim, n_layers, B) bytes of DEVICE
+ *             memory, no initialisation needed; one size serves every entry
+ *             point.  A call first writes each layer's (w, u_hat, b, w.u_hat)
+ *             there with one small launch, which every kernel of the call
+ *             reads, so nothing is cached between calls.
+ * In floats, with LPR = 1 (D <= 16), 16 (D <= 64) or 64 lanes per row,
+ * DP = D rounded up to a multiple of LPR, PW = L * (2 D + 2) + 4 and r64(n) = n
+ * rounded up to a multiple of 64, the workspace holds
+ *   r64(L * (2 DP + 8)) + r64(PW) + r64(max(U * PW, 4 * F)) + (L > 10 ? r64(L * B) : 0)
+ * where F = min(1024, ceil(B * LPR / 256)) blocks of the forward grid (at
+ * least 1) and U the records of the reverse grid: C = min(256, ceil(B * LPR /
+ * 256)) blocks when PW <= 3072, else 4 records for each of min(C, max(4,
+ * 2^20 / PW)) blocks.  The last term is the per-(row, layer) tanh tape of
+ * stacks deeper than 10 layers (shallower ones keep it in registers).
+ * Argument errors (NULL, alignment, shape, batch) are returned before any
+ * launch; B == 0 zeroes loss_terms / grads with memset nodes and launches no
+ * kernel.  Deterministic: per-block partial sums added in block order by a
+ * one-block follow-up launch; the grids depend on (D, L, B) only, so two calls
+ * agree bitwise.  No float atomics, no allocation, no host synchronisation. */
+#define CNF_PLANAR_MAX_LAYERS 64
+
+/* 3 * L tensors, L * (2 D + 1) floats. */
+int cnf_planar_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats);
+int cnf_planar_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B, size_t* bytes);
+
+/* Flow.forward of the stack: z [B][D] (= zs[-1]), logdet [B] (the sum over
+ * layers), z_all [L][B][D] (the zs list); each may be NULL. */
+int cnf_planar_forward(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, float* z, float* logdet, float* z_all, int64_t B,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Forward + loss terms, as cnf_forward_loss: loss_terms[3] = {sum of per-row
+ * loss, sum of ce, sum of ld} for CNF_LOSS_CAL / CNF_LOSS_CE; z, logdet may be
+ * NULL.  A label outside [0, D) makes the terms NaN. */
+int cnf_planar_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
+                            const float* x, const int64_t* y, int32_t loss_kind, float det,
+                            float* z, float* logdet, float* loss_terms, int64_t B,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Reverse mode of cnf_planar_forward, as cnf_vjp: upstream gz [B][D], gz_all
+ * [L][B][D], gld [B] (each may be NULL = zero); writes grads
+ * [cnf_planar_param_count] (per layer w, u, b; overwritten) and dx [B][D]
+ * (may be NULL).  The forward pass is recomputed inside; the only tape is one
+ * tanh value per (row, layer). */
+int cnf_planar_vjp(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                   const float* gz, const float* gz_all, const float* gld, float* grads,
+                   float* dx, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fused forward + loss + reverse mode, as cnf_loss_vjp: loss_terms[3] (sums
+ * over this batch), grads = grad_scale * d(sum of the per-row loss)/d(params),
+ * dx [B][D] = grad_scale * d(sum of the per-row loss)/dx, may be NULL. */
+int cnf_planar_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
+                        const float* x, const int64_t* y, int32_t loss_kind, float det,
+                        float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"

@@ -14,6 +14,8 @@
 #   sweep        tools/batch_sweep.py loss / forward (2^16..2^24 rows)
 #   mix          tools/ubench/mix_rate (VALU / MFMA co-issue rates)
 #   calib        the calibrator-fit epoch variant (bench.calibrator_epoch_rate)
+#   planar       planar flows: tests/test_gpu_planar.py at the small shapes, then its 2^20-row
+#                test, then tools/planar_bench.py -- each only after the one before passed
 #   abbits       tools/ab/ab_bits.py (output fingerprints) for the shipped lib and every tools/ab/lib*.so
 #   abtrace      tools/sgpr_trace.py for every tools/ab/lib*.so (trace builds) at AB_TRACE_B rows
 #   abpower      tools/power_probe.py (board power, energy per row) for the shipped lib and every tools/ab/lib*.so
@@ -33,6 +35,7 @@ run() {
   local t0=$(date +%s)
   timeout -k 10 "$@" > gpurun_out/$name.log 2>&1
   local rc=$?
+  LAST_RC=$rc
   echo "$name rc=$rc ($(( $(date +%s) - t0 ))s)"
   tail -n ${TAILN:-4} gpurun_out/$name.log | grep -v amdgpu.ids
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "stopping after $name (rc=$rc)"; exit $rc; fi
@@ -49,6 +52,10 @@ for step in "$@"; do
     sweep) run sweep_loss 300 python tools/batch_sweep.py loss && run sweep_fwd 300 python tools/batch_sweep.py forward ;;
     mix) run mix_rate 120 tools/ubench/mix_rate ;;
     calib) run calib 300 python -c "import json, torch, bench; print(json.dumps(bench.calibrator_epoch_rate(torch.device('cuda:0'))))" ;;
+    planar)
+      run planar_small 400 python -u -m pytest tests/test_gpu_planar.py -m gpu -q -k "not million"
+      [ $LAST_RC -eq 0 ] && run planar_million 200 python -u -m pytest tests/test_gpu_planar.py -m gpu -q -k "million"
+      [ $LAST_RC -eq 0 ] && TAILN=9 run planar_bench 400 python tools/planar_bench.py --out - ;;
     ab)
       for lib in tools/ab/lib*.so; do
         [ -e "$lib" ] || continue
