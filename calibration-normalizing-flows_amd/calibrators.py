@@ -8,9 +8,16 @@ step is ONE fused native launch (forward + calibrator loss + reverse mode,
 cnf_loss_vjp) followed by the optimizer step, and the per-epoch evaluation is
 ONE fused forward + loss launch (cnf_forward_loss); history entries stay
 device tensors, as in the reference, so no step synchronises the host.
-A flow made of PlanarLayers (flows._factory.PlanarFlow) trains the same way on
-its own kernels: cnf_planar_loss_vjp per batch, then torch's own Adam step, and
-cnf_planar_forward_loss per evaluation batch.
+A flow made of PlanarLayers (flows._factory.PlanarFlow) runs the same schedule
+on its own kernels: cnf_planar_loss_vjp into a persistent flat gradient and one
+native Adam launch (cnf_adam_step_tensors) per batch, cnf_planar_forward_loss
+per evaluation batch, and -- after one eager epoch -- chunks of epochs replayed
+as one captured HIP graph.  An optimizer the native Adam does not reproduce
+(cnf_hip.adam.supports) keeps torch's own step after each
+cnf_planar_loss_vjp.  `predict` / `evaluate` / `detection_curves` of a planar
+calibrator on a ROCm device are one cnf_planar_predict launch on a resident
+replica, and `evaluate` copies only the 4 + 3 * bins record words to the host.
+CNF_PLANAR_NATIVE=0 keeps a planar flow on torch ops throughout.
 Any other flow (or a CPU device) runs the reference's own torch loop.
 
 The scaling baselines -- TempScalingCalibrator, MLRCalibrator,
@@ -433,21 +440,35 @@ def _loader_order(n):
 class _EpochRunner:
     """One training epoch of TorchFlowCalibrator.fit on the fused kernels
     (calibrators.py:284-317): gather the pass's rows in loader order, per
-    batch cnf_loss_vjp + Adam, then the eval pass's cnf_forward_loss per batch,
-    whose LAST batch's sums are the epoch's history terms."""
+    batch the stack's fused loss + reverse mode and one Adam launch, then the
+    eval pass's fused forward + loss per batch, whose LAST batch's sums are the
+    epoch's history terms.
+
+    `stack` is a CouplingStack or a PlanarStack; the runner uses
+    loss_and_grads(x, y, grad_scale=, grads_out=, terms_out=),
+    forward_loss(x, y, terms_out=), reserve_workspace / release_workspace and
+    invalidate() (no-ops where a stack has nothing to do).  The flat gradient
+    and the terms of the batches nobody reads are persistent buffers, so a
+    captured epoch allocates neither."""
 
     def __init__(self, stack, adam, logits, target, bs):
         self.stack, self.adam, self.x, self.y, self.bs = stack, adam, logits, target, bs
         self.N = logits.shape[0]
         self.nb = (self.N + bs - 1) // bs
+        dev = logits.device
+        self.flat = torch.empty(stack.param_count(), dtype=torch.float32, device=dev)
+        self.step_terms = torch.empty(3, dtype=torch.float32, device=dev)
+        self.eval_terms = torch.empty(3, dtype=torch.float32, device=dev)
+        stack.reserve_workspace(min(bs, self.N), dev)
 
     def body(self, order_tr, order_ev, terms_out, sched=None):
-        from cnf_hip import vjp as V
         N, bs = self.N, self.bs
         xs, ys = self.x.index_select(0, order_tr), self.y.index_select(0, order_tr)
         for b, s in enumerate(range(0, N, bs)):
             xb, yb = xs[s:s + bs], ys[s:s + bs]
-            _, grads, _ = V.loss_and_grads(self.stack, xb, yb, grad_scale=1.0 / xb.shape[0])
+            _, grads, _ = self.stack.loss_and_grads(xb, yb, grad_scale=1.0 / xb.shape[0],
+                                                    grads_out=self.flat,
+                                                    terms_out=self.step_terms)
             if sched is None:
                 self.adam.step(grads)
             else:
@@ -456,7 +477,7 @@ class _EpochRunner:
         for s in range(0, N, bs):
             last = s + bs >= N
             self.stack.forward_loss(xe[s:s + bs], ye[s:s + bs],
-                                    terms_out=terms_out if last else None)
+                                    terms_out=terms_out if last else self.eval_terms)
 
     def eager_epoch(self, terms_out):
         dev = self.x.device
@@ -540,9 +561,11 @@ class TorchFlowCalibrator(Calibrator):
             with torch.cuda.device(logits.device):
                 history = self._fit_native(stack, logits, target, epochs, batch_size)
         elif _planar_stack(self.flow, self.dev) is not None:
+            from cnf_hip import adam
+            pstack = _planar_stack(self.flow, self.dev)
+            fit = self._fit_native if adam.supports(self.optimizer) else self._fit_planar
             with torch.cuda.device(logits.device):
-                history = self._fit_planar(_planar_stack(self.flow, self.dev), logits, target,
-                                           epochs, batch_size)
+                history = fit(pstack, logits, target, epochs, batch_size)
         else:
             history = self._fit_torch(logits, target, epochs, batch_size)
         self.flow.cpu()
@@ -588,7 +611,9 @@ class TorchFlowCalibrator(Calibrator):
     def _fit_native(self, stack, logits, target, epochs, batch_size):
         """Same schedule on the fused kernels: one cnf_loss_vjp launch plus one
         cnf_adam_step launch per training batch, one cnf_forward_loss launch per
-        evaluation batch.  Each pass over the data draws its order exactly as
+        evaluation batch (a PlanarStack: cnf_planar_loss_vjp,
+        cnf_adam_step_tensors, cnf_planar_forward_loss).  Each pass over the
+        data draws its order exactly as
         the reference's DataLoader(shuffle=True) does (_loader_order), so
         minibatch runs see the reference's batches and the eval history keeps
         the reference's last-batch value (calibrators.py:274-317).
@@ -618,17 +643,19 @@ class TorchFlowCalibrator(Calibrator):
             e += 1
         adam.store_into(self.optimizer)
         stack.invalidate()  # drop blobs / workspaces captured into a graph pool
+        stack.release_workspace()
         hist = terms_all[:epochs] / N
         return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
                 'log_det': list(hist[:, 2].unbind(0))}
 
     def _fit_planar(self, stack, logits, target, epochs, batch_size):
-        """The same schedule for an all-planar flow: per training batch one
-        cnf_planar_loss_vjp launch whose flat gradient is viewed into each
-        parameter's .grad, then torch's own Adam step (the optimizer state
-        stays torch's); per evaluation batch one cnf_planar_forward_loss
-        launch.  Every pass draws its order as the reference's
-        DataLoader(shuffle=True) does (_loader_order), and the history keeps
+        """The planar fit under an optimizer the native Adam does not reproduce
+        (cnf_hip.adam.supports is false: AdamW, amsgrad, ...), every epoch
+        eager: per training batch one cnf_planar_loss_vjp launch whose flat
+        gradient is viewed into each parameter's .grad, then the torch
+        optimizer's own step (its state stays torch's); per evaluation batch
+        one cnf_planar_forward_loss launch.  Every pass draws its order as the
+        reference's DataLoader(shuffle=True) does (_loader_order), and the history keeps
         the last batch's sums over N (calibrators.py:274-317)."""
         N = logits.shape[0]
         bs = max(1, int(batch_size))
@@ -679,6 +706,8 @@ class TorchFlowCalibrator(Calibrator):
         flow = self._device_flow()
         stack = _native_stack(flow, self.dev, need_vjp=False)
         if stack is None:
+            stack = _planar_stack(flow, self.dev)
+        if stack is None:
             return None
         x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
         if self._lp_dev is None:
@@ -690,8 +719,9 @@ class TorchFlowCalibrator(Calibrator):
         """Calibrator.predict (calibrators.py:40-44 with predict_post, :330-353):
         centring, the flow, softmax and the prior correction
         softmax(log(p + 1e-7) - log_priors).  On a ROCm device this is ONE fused
-        launch (cnf_predict) on a resident replica of the flow, with one H2D
-        copy of the logits and one D2H copy of the probabilities."""
+        launch (cnf_predict; cnf_planar_predict for a planar flow) on a
+        resident replica of the flow, with one H2D copy of the logits and one
+        D2H copy of the probabilities."""
         probs = self._predict_device(logits)
         if probs is not None:
             return probs.cpu().numpy().astype(np.float64)

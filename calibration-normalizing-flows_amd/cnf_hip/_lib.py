@@ -38,14 +38,14 @@ EXPORTS = (
     "cnf_param_count", "cnf_param_tensor_count", "cnf_prepared_bytes", "cnf_prepare",
     "cnf_forward", "cnf_inverse", "cnf_forward_loss_workspace_bytes", "cnf_forward_loss",
     "cnf_predict", "cnf_vjp_workspace_bytes", "cnf_vjp", "cnf_loss_vjp", "cnf_adam_step",
-    "cnf_adam_step_sched", "cnf_adam_step_guarded",
+    "cnf_adam_step_sched", "cnf_adam_step_guarded", "cnf_adam_step_tensors",
     "cnf_vjp_inverse_workspace_bytes", "cnf_vjp_inverse", "cnf_guard_nonfinite",
     "cnf_metrics_record_words", "cnf_metrics_workspace_bytes", "cnf_metrics",
     "cnf_scaling_sums_words", "cnf_scaling_workspace_bytes", "cnf_scaling_loss_grad",
     "cnf_scaling_predict",
     "cnf_pav_predict",
     "cnf_planar_param_count", "cnf_planar_workspace_bytes", "cnf_planar_forward",
-    "cnf_planar_forward_loss", "cnf_planar_vjp", "cnf_planar_loss_vjp",
+    "cnf_planar_forward_loss", "cnf_planar_predict", "cnf_planar_vjp", "cnf_planar_loss_vjp",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -112,6 +112,8 @@ def _bind(lib):
                                                P]),
         "cnf_adam_step_guarded": (ctypes.c_int, [D, ctypes.POINTER(P), P, P, P, I64, DB, P, DB,
                                                  DB, DB, DB, P, P]),
+        "cnf_adam_step_tensors": (ctypes.c_int, [I32, ctypes.POINTER(I64), ctypes.POINTER(P), P, P,
+                                                 P, I64, DB, P, DB, DB, DB, DB, P, P]),
         "cnf_guard_nonfinite": (ctypes.c_int, [P, I64, P, P]),
         "cnf_metrics_record_words": (ctypes.c_int, [I32, ctypes.POINTER(I64)]),
         "cnf_metrics_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
@@ -131,6 +133,8 @@ def _bind(lib):
                                               ctypes.c_size_t, P]),
         "cnf_planar_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P,
                                                    P, I64, P, ctypes.c_size_t, P]),
+        "cnf_planar_predict": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
         "cnf_planar_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, P, P, I64, P,
                                           ctypes.c_size_t, P]),
         "cnf_planar_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, F, P, P,

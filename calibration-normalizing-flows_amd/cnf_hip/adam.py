@@ -1,5 +1,10 @@
-"""On-device Adam over a coupling stack's parameters in ONE launch
-(cnf_adam_step, include/cnf.h), fed by the flat gradient of cnf_loss_vjp:
+"""On-device Adam over a stack's parameters in ONE launch (cnf_adam_step,
+include/cnf.h), fed by the flat gradient of cnf_loss_vjp /
+cnf_planar_loss_vjp.  Any stack that offers `param_tensors()` and
+`param_count()` works: a CouplingStack goes through the cnf_desc entry points
+(cnf_adam_step, _sched, _guarded), a stack without a `desc` (PlanarStack)
+through cnf_adam_step_tensors, the same kernel over an explicit tensor list.
+It is
 the optimizer half of the calibrator's fused training step (SURVEY 8(f) rank 1;
 the reference steps torch.optim.Adam at its defaults, calibrators.py:239-295).
 Same update as torch.optim.Adam (amsgrad off), with torch's scalar rounding
@@ -46,7 +51,8 @@ def group_hparams(torch_adam, stack):
 
 
 class StackAdam:
-    """Adam state (two flat moment buffers) for one CouplingStack."""
+    """Adam state (two flat moment buffers) for one stack (CouplingStack or
+    PlanarStack)."""
 
     def __init__(self, stack, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.stack = stack
@@ -126,20 +132,53 @@ class StackAdam:
             self._m, self._v = self._m.to(dev), self._v.to(dev)
         return ps, dev
 
+    def _tensors_call(self, ps, dev, flat_grads, sched, skip):
+        """cnf_adam_step_tensors: the stack has no cnf_desc."""
+        n = len(ps)
+        arr = (ctypes.c_void_p * max(n, 1))(*[p.data_ptr() for p in ps])
+        numel = (ctypes.c_int64 * max(n, 1))(*[p.numel() for p in ps])
+        st = _lib.lib().cnf_adam_step_tensors(
+            ctypes.c_int32(n), numel, arr, _ptr(flat_grads), _ptr(self._m), _ptr(self._v),
+            ctypes.c_int64(self.t), ctypes.c_double(self.lr), _ptr(sched),
+            ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
+            ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _ptr(skip),
+            _stream(dev))
+        _lib.check("cnf_adam_step_tensors", st)
+
+    def _check_step(self, ps, dev, flat_grads):
+        for p in ps:
+            if not p.is_contiguous():
+                raise ValueError("StackAdam needs contiguous parameters")
+        if flat_grads.numel() != self.stack.param_count() or flat_grads.dtype != torch.float32 \
+                or not flat_grads.is_contiguous() or flat_grads.device != dev:
+            raise ValueError("StackAdam: the flat gradient must be contiguous fp32 [%d] on %s"
+                             % (self.stack.param_count(), dev))
+
+    def _done(self, ps):
+        # the kernel wrote the parameters behind autograd's back: bump their
+        # version counters, so every prepared-weight cache keyed on them (this
+        # stack's and any other binding's) rebuilds
+        for p in ps:
+            torch.autograd.graph.increment_version(p)
+        stats["adam"] = stats.get("adam", 0) + 1
+
     def step_sched(self, flat_grads, sched):
         """One step whose scalars come from the device tensor `sched` [2]
         (graph capture: replays any step).  Advances the host step count."""
         ps, dev = self._ensure_state()
         self.t += 1
+        if not hasattr(self.stack, "desc"):
+            self._check_step(ps, dev, flat_grads)
+            with torch.cuda.device(dev):
+                self._tensors_call(ps, dev, flat_grads, sched, None)
+            return self._done(ps)
         arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
         st = _lib.lib().cnf_adam_step_sched(
             ctypes.byref(self.stack.desc), arr, _ptr(flat_grads), _ptr(self._m), _ptr(self._v),
             _ptr(sched), ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
             ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _stream(dev))
         _lib.check("cnf_adam_step_sched", st)
-        for p in ps:
-            torch.autograd.graph.increment_version(p)
-        stats["adam"] = stats.get("adam", 0) + 1
+        self._done(ps)
 
     def step(self, flat_grads, skip=None):
         """One step.  skip: a device int32 flag (NonFiniteGuard.flag) read by
@@ -149,12 +188,17 @@ class StackAdam:
         for p in ps:
             if not p.is_contiguous():
                 raise ValueError("StackAdam needs contiguous parameters")
+        if skip is not None and (skip.dtype != torch.int32 or skip.device != dev):
+            raise ValueError("StackAdam.step: skip must be a device int32 flag on %s" % dev)
         self.t += 1
+        if not hasattr(self.stack, "desc"):
+            self._check_step(ps, dev, flat_grads)
+            with torch.cuda.device(dev):
+                self._tensors_call(ps, dev, flat_grads, None, skip)
+            return self._done(ps)
         arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
         lib = _lib.lib()
         if skip is not None:
-            if skip.dtype != torch.int32 or skip.device != dev:
-                raise ValueError("StackAdam.step: skip must be a device int32 flag on %s" % dev)
             st = lib.cnf_adam_step_guarded(
                 ctypes.byref(self.stack.desc), arr, _ptr(flat_grads), _ptr(self._m),
                 _ptr(self._v), ctypes.c_int64(self.t), ctypes.c_double(self.lr), None,
@@ -169,9 +213,4 @@ class StackAdam:
                                    ctypes.c_double(self.betas[1]), ctypes.c_double(self.eps),
                                    ctypes.c_double(self.weight_decay), _stream(dev))
             _lib.check("cnf_adam_step", st)
-        # the kernel wrote the parameters behind autograd's back: bump their
-        # version counters, so every prepared-weight cache keyed on them (this
-        # stack's and any other binding's) rebuilds
-        for p in ps:
-            torch.autograd.graph.increment_version(p)
-        stats["adam"] = stats.get("adam", 0) + 1
+        self._done(ps)

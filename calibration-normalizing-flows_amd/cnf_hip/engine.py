@@ -25,7 +25,7 @@ from . import _lib
 # counts the launches that went through the torch.library operators
 stats = {"forward": 0, "inverse": 0, "prepare": 0, "vjp": 0, "loss_vjp": 0, "predict": 0,
          "metrics": 0, "torch_ops": 0, "planar_forward": 0, "planar_vjp": 0,
-         "planar_loss_vjp": 0}
+         "planar_loss_vjp": 0, "planar_predict": 0}
 
 # Dispatch through torch.ops.cnf (C++ operators, autograd in C++) when
 # libcnf_torch.so is built; False: the ctypes calls of the same C ABI.
@@ -260,6 +260,21 @@ class CouplingStack:
         _lib.check("cnf_forward_loss", st)
         stats["forward"] += 1
         return terms, z, ld
+
+    def loss_and_grads(self, x, y, **kw):
+        """Fused forward + loss + reverse mode: vjp.loss_and_grads(self, ...)
+        as a method, the form the calibrator's epoch runner calls on either
+        kind of stack."""
+        from .vjp import loss_and_grads
+        return loss_and_grads(self, x, y, **kw)
+
+    def reserve_workspace(self, B, device):
+        """The epoch runner's hook; nothing to do here: this stack's workspaces
+        are per-stream caches, and the ones a capture creates live in the
+        graph's private pool."""
+
+    def release_workspace(self):
+        pass
 
     def predict(self, x, log_priors, want_logdet=False):
         """Calibrated probabilities softmax(log(softmax(flow(x - mean x)) + 1e-7)

@@ -3,7 +3,13 @@
 `PlanarStack` binds a run of PlanarLayers of one width to the fused kernels:
 one launch for the forward + log-det (every layer's output optional), one for
 the forward + loss terms, one for the reverse mode, one for the fused
-forward + loss + reverse mode.  The layers keep owning `w`, `u`, `b`; the stack
+forward + loss + reverse mode, and one for the calibrator's predict
+(`predict`: centring, the stack, both softmaxes and the prior correction,
+cnf_planar_predict).  `cnf_hip.adam.StackAdam` steps the stack's parameters
+in one launch (cnf_adam_step_tensors) from the flat gradient `loss_and_grads`
+writes, and `invalidate()` is a no-op, so the calibrator's epoch runner and
+its HIP-graph replay drive a PlanarStack as they drive a CouplingStack.  The
+layers keep owning `w`, `u`, `b`; the stack
 passes their device pointers on every call and the library re-derives `u_hat`
 inside the call, so there is no prepared state to invalidate.  Buffers are
 torch allocations on the input's device and the launches go to torch's current
@@ -58,6 +64,7 @@ class PlanarStack:
         self.L = len(self.layers)
         self.dim = int(self.layers[0].w.numel())
         self._params = [t for ly in self.layers for t in _layer_tensors(ly)]
+        self._own_ws = None
 
     @staticmethod
     def compatible(layers, device=None):
@@ -110,13 +117,30 @@ class PlanarStack:
             raise ValueError("expected [B, %d] rows, got %s" % (self.dim, tuple(x.shape)))
         return x.contiguous()
 
+    def reserve_workspace(self, B, device):
+        """Hold one private workspace for batches up to B rows on `device`,
+        whatever stream the calls go to (the calibrator's fit: eager epochs
+        and the capturing stream of its HIP graph use the same buffer, which
+        exists before the capture).  The caller keeps this stack's calls on
+        one stream at a time until release_workspace()."""
+        n = workspace_bytes(self.dim, self.L, B)
+        self._own_ws = (torch.empty(max(n, 16), dtype=torch.uint8, device=device), int(B))
+
+    def release_workspace(self):
+        self._own_ws = None
+
+    def _ws(self, B, dev):
+        if self._own_ws is not None and B <= self._own_ws[1] and self._own_ws[0].device == dev:
+            return self._own_ws[0], workspace_bytes(self.dim, self.L, B)
+        return _workspace(self.dim, self.L, B, dev)
+
     # ---------------------------------------------------------------- launches
     def run(self, x, want_all=False, want_final=True):
         """(final [B, D] or None, logdet [B], all [L, B, D] or None): one
         cnf_planar_forward call."""
         x = self._check_input(x.detach())
         B, dev = x.shape[0], x.device
-        ws, n = _workspace(self.dim, self.L, B, dev)
+        ws, n = self._ws(B, dev)
         ld = torch.empty(B, dtype=torch.float32, device=dev)
         allt = torch.empty(self.L, B, self.dim, dtype=torch.float32, device=dev) \
             if want_all else None
@@ -138,7 +162,7 @@ class PlanarStack:
         x = self._check_input(x.detach())
         y = y.contiguous().to(torch.int64)
         B, dev = x.shape[0], x.device
-        ws, n = _workspace(self.dim, self.L, B, dev)
+        ws, n = self._ws(B, dev)
         terms = torch.empty(3, dtype=torch.float32, device=dev) if terms_out is None else terms_out
         if terms.numel() != 3 or terms.dtype != torch.float32 or terms.device != dev \
                 or not terms.is_contiguous():
@@ -159,7 +183,7 @@ class PlanarStack:
         all_grads else z_final, log-det): one cnf_planar_vjp call."""
         x = self._check_input(x.detach())
         B, dev = x.shape[0], x.device
-        ws, n = _workspace(self.dim, self.L, B, dev)
+        ws, n = self._ws(B, dev)
         grads = torch.empty(self.param_count(), dtype=torch.float32, device=dev)
         dx = torch.empty_like(x) if need_dx else None
         gz = gza = None
@@ -190,7 +214,7 @@ class PlanarStack:
         x = self._check_input(x.detach())
         y = y.contiguous().to(torch.int64)
         B, dev = x.shape[0], x.device
-        ws, n = _workspace(self.dim, self.L, B, dev)
+        ws, n = self._ws(B, dev)
         P = self.param_count()
         grads = torch.empty(P, dtype=torch.float32, device=dev) if grads_out is None else grads_out
         terms = torch.empty(3, dtype=torch.float32, device=dev) if terms_out is None else terms_out
@@ -209,6 +233,32 @@ class PlanarStack:
         _lib.check("cnf_planar_loss_vjp", st)
         stats["planar_loss_vjp"] += 1
         return terms, grads, dx
+
+    def predict(self, x, log_priors, want_logdet=False):
+        """Calibrated probabilities softmax(log(softmax(flow(x - mean x)) + 1e-7)
+        - log_priors) (Calibrator.predict, calibrators.py:40-44, 330-353): one
+        cnf_planar_predict call.  Returns probs [B, D], or (probs, logdet [B]
+        of the centred rows)."""
+        x = self._check_input(x.detach())
+        B, dev = x.shape[0], x.device
+        lp = torch.as_tensor(log_priors, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        if lp.numel() != self.dim:
+            raise ValueError("log_priors must have %d entries" % self.dim)
+        ws, n = self._ws(B, dev)
+        probs = torch.empty_like(x)
+        ld = torch.empty(B, dtype=torch.float32, device=dev) if want_logdet else None
+        with torch.cuda.device(dev):
+            st = _lib.lib().cnf_planar_predict(
+                ctypes.c_int32(self.dim), ctypes.c_int32(self.L), self._ptrs(), _ptr(x), _ptr(lp),
+                _ptr(probs), _ptr(ld), ctypes.c_int64(B), _ptr(ws), ctypes.c_size_t(n),
+                _stream(dev))
+        _lib.check("cnf_planar_predict", st)
+        stats["planar_predict"] += 1
+        return (probs, ld) if want_logdet else probs
+
+    def invalidate(self):
+        """Nothing is prepared between calls (every call re-derives u_hat), so
+        there is nothing to forget; kept so callers treat both stacks alike."""
 
     def split(self, flat):
         """Views of a flat gradient, one per parameter tensor."""

@@ -9,11 +9,14 @@
 //   v  = beta2 * v + (1 - beta2) * g * g          (exp_avg_sq.mul_().addcmul_())
 //   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // The moments live in two flat device buffers the caller owns (cnf_param_count
-// floats each, zero before the first step).
+// floats each, zero before the first step).  The kernel knows only a table of
+// tensors and flat offsets: cnf_adam_step_tensors takes that list directly (a
+// planar stack's w, u, b), and the cnf_desc entry points derive it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "cnf_internal.h"
 
@@ -72,16 +75,20 @@ using namespace cnf;
 
 namespace {
 
-int adam_launch(const cnf_desc* desc, float* const* params, const float* grads, float* exp_avg,
-                float* exp_avg_sq, int64_t step, double lr, double beta1, double beta2, double eps,
-                double weight_decay, const float* sched, const int32_t* skip, void* stream) {
-  Shape s;
-  int st = derive_shape(desc, &s);
-  if (st != CNF_OK) return st;
+// The launches over an explicit tensor list: numel[nt] sizes in flat-gradient
+// order.  Every argument is checked before the first launch.
+int adam_tensors(int nt, const int64_t* numel, float* const* params, const float* grads,
+                 float* exp_avg, float* exp_avg_sq, int64_t step, double lr, double beta1,
+                 double beta2, double eps, double weight_decay, const float* sched,
+                 const int32_t* skip, void* stream) {
+  if (nt < 0) return CNF_ERR_DESC;
   if (!sched && step < 1) return CNF_ERR_DESC;
-  const int nt = s.L * s.nets * s.n_lin * 2;
   if (nt == 0) return CNF_OK;
-  if (!params || !grads || !exp_avg || !exp_avg_sq) return CNF_ERR_NULL;
+  if (!numel || !params || !grads || !exp_avg || !exp_avg_sq) return CNF_ERR_NULL;
+  for (int i = 0; i < nt; ++i) {
+    if (numel[i] < 0) return CNF_ERR_DESC;
+    if (!params[i]) return CNF_ERR_NULL;
+  }
   const double bc1 = sched ? 1.0 : 1.0 - std::pow(beta1, (double)step);
   const double bc2 = sched ? 1.0 : 1.0 - std::pow(beta2, (double)step);
   AdamArgs a{};
@@ -97,43 +104,48 @@ int adam_launch(const cnf_desc* desc, float* const* params, const float* grads, 
   a.wd = (float)weight_decay;
   a.step_size = (float)(lr / bc1);
   a.bc2_sqrt = (float)std::sqrt(bc2);
-  // tensor sizes in ABI order: per layer, per net, per Linear: W then b
   int64_t off = 0;
-  int k = 0, first = 0;
-  auto flush = [&](int n_here) {
-    if (n_here == 0) return;
+  for (int first = 0; first < nt; first += kAdamTensors) {
+    // a chunk's offsets start at its first tensor's flat position
+    const int n_here = std::min(kAdamTensors, nt - first);
     int64_t maxn = 0;
-    for (int i = 0; i < n_here; ++i) maxn = std::max(maxn, a.off[i + 1] - a.off[i]);
+    for (int k = 0; k < n_here; ++k) {
+      a.p[k] = params[first + k];
+      a.off[k] = off;
+      off += numel[first + k];
+      maxn = std::max(maxn, numel[first + k]);
+    }
+    a.off[n_here] = off;
     const unsigned gx = (unsigned)std::min<int64_t>((maxn + 255) / 256, 64);
+    if (gx == 0) continue;  // every tensor of the chunk is empty
     hipLaunchKernelGGL(k_adam, dim3(gx, (unsigned)n_here), dim3(256), 0, (hipStream_t)stream, a);
-  };
-  for (int l = 0; l < s.L; ++l)
-    for (int n = 0; n < s.nets; ++n)
-      for (int i = 0; i < s.n_lin; ++i)
-        for (int wb = 0; wb < 2; ++wb) {
-          const int64_t cnt = wb == 0 ? (int64_t)s.units[i + 1] * s.units[i] : s.units[i + 1];
-          float* p = params[first + k];
-          if (!p) return CNF_ERR_NULL;
-          a.p[k] = p;
-          a.off[k] = off;
-          off += cnt;
-          a.off[k + 1] = off;
-          if (++k == kAdamTensors) {
-            // offsets of the next chunk restart from its first tensor's position
-            flush(k);
-            first += k;
-            const int64_t base = off;
-            k = 0;
-            a.off[0] = base;
-          }
-        }
-  flush(k);
+  }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
     set_hip_error(err);
     return CNF_ERR_HIP;
   }
   return CNF_OK;
+}
+
+// A coupling stack's tensor sizes in ABI order: per layer, per net, per
+// Linear: W then b.
+int adam_launch(const cnf_desc* desc, float* const* params, const float* grads, float* exp_avg,
+                float* exp_avg_sq, int64_t step, double lr, double beta1, double beta2, double eps,
+                double weight_decay, const float* sched, const int32_t* skip, void* stream) {
+  Shape s;
+  int st = derive_shape(desc, &s);
+  if (st != CNF_OK) return st;
+  std::vector<int64_t> numel;
+  numel.reserve((size_t)s.L * s.nets * s.n_lin * 2);
+  for (int l = 0; l < s.L; ++l)
+    for (int n = 0; n < s.nets; ++n)
+      for (int i = 0; i < s.n_lin; ++i) {
+        numel.push_back((int64_t)s.units[i + 1] * s.units[i]);
+        numel.push_back(s.units[i + 1]);
+      }
+  return adam_tensors((int)numel.size(), numel.data(), params, grads, exp_avg, exp_avg_sq, step, lr,
+                      beta1, beta2, eps, weight_decay, sched, skip, stream);
 }
 
 }  // namespace
@@ -166,4 +178,14 @@ extern "C" int cnf_adam_step_guarded(const cnf_desc* desc, float* const* params,
   if (!skip_flag) return CNF_ERR_NULL;
   return adam_launch(desc, params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps,
                      weight_decay, sched, skip_flag, stream);
+}
+
+extern "C" int cnf_adam_step_tensors(int32_t n_tensors, const int64_t* numel, float* const* params,
+                                     const float* grads, float* exp_avg, float* exp_avg_sq,
+                                     int64_t step, double lr, const float* sched, double beta1,
+                                     double beta2, double eps, double weight_decay,
+                                     const int32_t* skip_flag, void* stream) {
+  CNF_RANGE("cnf_adam_step_tensors");
+  return adam_tensors(n_tensors, numel, params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2,
+                      eps, weight_decay, sched, skip_flag, stream);
 }

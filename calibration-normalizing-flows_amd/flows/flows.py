@@ -20,6 +20,11 @@ Host tensors (CPU) run the same math with torch ops, as the reference does.
 Layers the native engine does not cover (AffineConstantLayer, RadialLayer --
 out of the hot-path scope) and mixed stacks run as torch ops, layer
 by layer.  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops as well.
+
+A planar stack's other launches hang off the same binding (cnf_hip/planar.py):
+the fused training step and loss evaluation, the calibrator's fused predict
+(cnf_planar_predict) and the one-launch Adam step (cnf_adam_step_tensors);
+calibrators.TorchFlowCalibrator drives them, HIP-graph epoch replay included.
 """
 import os
 import warnings

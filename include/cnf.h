@@ -228,6 +228,24 @@ int cnf_adam_step_guarded(const cnf_desc* desc, float* const* params, const floa
                           const float* sched, double beta1, double beta2, double eps,
                           double weight_decay, const int32_t* skip_flag, void* stream);
 
+/* The same kernel over an explicit tensor list, for parameters that no cnf_desc
+ * describes (a planar stack's w, u, b):
+ *   n_tensors   tensors in the list (0: nothing to do)
+ *   numel       HOST array of n_tensors sizes, in flat-gradient order: tensor i
+ *               owns grads / exp_avg / exp_avg_sq [sum numel[<i], + numel[i])
+ *   params      HOST array of n_tensors DEVICE pointers, updated in place
+ *   sched       NULL: (step, lr) as cnf_adam_step; else the DEVICE
+ *               {step_size, bc2_sqrt} of cnf_adam_step_sched (step, lr ignored)
+ *   skip_flag   NULL, or the DEVICE int32 flag of cnf_adam_step_guarded
+ * n_tensors < 0, numel < 0, or step < 1 without sched: CNF_ERR_DESC; a NULL
+ * table entry: CNF_ERR_NULL -- all before any launch.  More than 128 tensors
+ * go out as one launch per 128. */
+int cnf_adam_step_tensors(int32_t n_tensors, const int64_t* numel, float* const* params,
+                          const float* grads, float* exp_avg, float* exp_avg_sq,
+                          int64_t step, double lr, const float* sched, double beta1,
+                          double beta2, double eps, double weight_decay,
+                          const int32_t* skip_flag, void* stream);
+
 /* Device-side non-finite guard (failure detection; the counterpart of the
  * reference's NaN abort, run_experiment3D.py:129-131, without a host sync):
  * scans n floats of a DEVICE array (z, logdet, loss_terms, gradients ...) and
@@ -397,6 +415,18 @@ int cnf_planar_forward_loss(int32_t dim, int32_t n_layers, const float* const* p
                             const float* x, const int64_t* y, int32_t loss_kind, float det,
                             float* z, float* logdet, float* loss_terms, int64_t B,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* Calibrator.predict of a planar flow calibrator, per row:
+ *   xc = x - mean(x);  z = planar stack(xc);  p = softmax(z)
+ *   probs = softmax(log(p + 1e-7) - log_priors)
+ * in one pass that keeps the row in registers.  log_priors [D] DEVICE floats
+ * (as cnf_predict; a -inf entry makes every row NaN, as the reference's is);
+ * probs [B][D]; logdet [B] of the centred rows, may be NULL.  Same envelope,
+ * workspace function, prepare launch, argument validation, B == 0 rule and
+ * determinism as cnf_planar_forward. */
+int cnf_planar_predict(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, const float* log_priors, float* probs, float* logdet,
+                       int64_t B, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Reverse mode of cnf_planar_forward, as cnf_vjp: upstream gz [B][D], gz_all
  * [L][B][D], gld [B] (each may be NULL = zero); writes grads
