@@ -38,6 +38,14 @@ sklearn and no `np.float`); tensors are copied to the host for the fit.
 per-class tables and returns a ROCm fp32 tensor.  (The fit itself is not on
 the device yet: DESIGN.md section 7d.)
 
+`Calibrator.score` / `score_sums` is the one scoring interface of every
+calibrator.  A planar TorchFlowCalibrator scores in ONE fused launch that never
+stores the probabilities (cnf_planar_score).  DummyCalibrator (whose predict
+now also runs on the device), the four scaling calibrators, PAVCalibrator and
+a coupling flow score a ROCm tensor with their fused predict plus one
+cnf_metrics launch; host inputs go through predict() and the record of
+cnf_hip.metrics.  `evaluate` / `evaluate_sums` are unchanged.
+
 `Calibrator.detection_curves` scores predict() in the detection view (one-vs-rest
 log-likelihood ratios, empirical cross-entropy curves; cnf_hip/detection.py) in
 float64 on the host.
@@ -79,6 +87,24 @@ def _detection_curves(probs, target, priors, lims, bins):
                                     detection.prior_axis(lims, bins))
 
 
+def _on_device(a):
+    return torch.is_tensor(a) and a.is_cuda
+
+
+def _score_labels(target, device):
+    """int64 labels [B] on `device` of `target` (labels, or one-hot rows whose
+    argmax is the label), as they are: a label outside [0, D) is the record's
+    business (n_invalid)."""
+    if torch.is_tensor(target):
+        y = target.detach()
+        y = torch.argmax(y, dim=1) if y.dim() == 2 else y.reshape(-1)
+    else:
+        y = np.asarray(target)
+        y = np.argmax(y, axis=1) if y.ndim == 2 else y.reshape(-1)
+        y = torch.as_tensor(y.astype(np.int64))
+    return y.to(device=device, dtype=torch.int64)
+
+
 class Calibrator:
     """Abstract calibrator (calibrators.py:13-44)."""
 
@@ -118,6 +144,35 @@ class Calibrator:
                 "ece": M.expected_calibration_error(probs, target, bins=bins),
                 "accuracy": M.accuracy(probs, target), "n": int(probs.shape[0])}
 
+    def score_sums(self, logits, target, bins=15, record=None):
+        """The calibration record of predict(logits) against `target` (labels
+        or one-hot rows) as cnf_hip.metrics.CalibrationSums; `record` (an int64
+        tensor on the scoring device) accumulates over calls.  A ROCm tensor
+        stays on the device: predict, then one cnf_metrics launch -- or, where
+        a subclass has a fused score kernel, that ONE launch, which leaves the
+        same words without storing the probabilities.  Host inputs are scored
+        from predict()'s float64 probabilities."""
+        from cnf_hip.metrics import CalibrationSums, calibration_record
+        if torch.is_tensor(logits) and not logits.is_cuda:
+            logits = logits.detach().numpy()
+        probs = self.predict(logits)
+        if not torch.is_tensor(probs):
+            probs = torch.as_tensor(np.asarray(probs))
+        y = _score_labels(target, probs.device)
+        return CalibrationSums(calibration_record(probs, y, bins, record), bins)
+
+    def score(self, logits, target, bins=15):
+        """{"nll", "ece", "accuracy", "n"} of predict(logits) against `target`:
+        score_sums for a ROCm tensor (only the 4 + 3 * bins record words reach
+        the host), evaluate()'s float64 host path for anything else."""
+        if _on_device(logits):
+            return self.score_sums(logits, target, bins).as_dict()
+        if torch.is_tensor(logits):
+            logits = logits.detach().numpy()
+        if torch.is_tensor(target):
+            target = target.detach().cpu().numpy()
+        return self.evaluate(logits, target, bins)
+
     def detection_curves(self, logits, target, priors=None, lims=(-2.5, 2.5), bins=100):
         """The detection view of predict(logits) against `target` (labels or
         one-hot rows) as cnf_hip.detection.EceCurveSums: the notebooks' steps
@@ -133,6 +188,15 @@ class DummyCalibrator(Calibrator):
 
     def predict_post(self, logits):
         return softmax(logits, axis=1)
+
+    def predict(self, logits):
+        """A ROCm tensor stays on the device: the scalar scaling kind with
+        a = 1 and no bias is softmax of the centred logits followed by the
+        prior correction (one cnf_scaling_predict launch, fp32 result)."""
+        if _on_device(logits):
+            from cnf_hip import scaling
+            return scaling.predict(logits, scaling.SCALAR, [1.0], None, self.log_priors)
+        return super().predict(logits)
 
 
 class _ScalingCalibrator(Calibrator):
@@ -698,20 +762,33 @@ class TorchFlowCalibrator(Calibrator):
             self._replica = (key, rep)
         return self._replica[1]
 
+    def _device_stack(self, logits):
+        """(stack, x, planar): the native stack of the resident replica, the
+        logits as an fp32 tensor on self.dev and whether the stack is a
+        PlanarStack; (None, None, False) when no native stack serves this flow
+        there."""
+        if torch.device(self.dev).type != "cuda":
+            return None, None, False
+        flow = self._device_flow()
+        stack, planar = _native_stack(flow, self.dev, need_vjp=False), False
+        if stack is None:
+            stack, planar = _planar_stack(flow, self.dev), True
+        if stack is None:
+            return None, None, False
+        if _on_device(logits):
+            x = logits.detach().to(device=self.dev, dtype=torch.float)
+        else:
+            x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
+        if self._lp_dev is None:
+            self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float, device=self.dev)
+        return stack, x, planar
+
     def _predict_device(self, logits):
         """predict()'s fp32 probabilities as a tensor on self.dev, or None when
         no native stack serves this flow there (then predict() runs on the host)."""
-        if torch.device(self.dev).type != "cuda":
-            return None
-        flow = self._device_flow()
-        stack = _native_stack(flow, self.dev, need_vjp=False)
-        if stack is None:
-            stack = _planar_stack(flow, self.dev)
+        stack, x, _ = self._device_stack(logits)
         if stack is None:
             return None
-        x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
-        if self._lp_dev is None:
-            self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float, device=self.dev)
         with torch.no_grad():
             return stack.predict(x, self._lp_dev)
 
@@ -747,6 +824,35 @@ class TorchFlowCalibrator(Calibrator):
     def evaluate(self, logits, target, bins=15):
         """{"nll", "ece", "accuracy", "n"} of predict(logits), from evaluate_sums."""
         return self.evaluate_sums(logits, target, bins).as_dict()
+
+    def score_sums(self, logits, target, bins=15, record=None):
+        """evaluate_sums' record (logits: arrays or tensors, ROCm ones
+        included).  A planar flow on a ROCm device scores in ONE
+        cnf_planar_score launch on the resident replica; a coupling flow keeps
+        its fused predict plus one cnf_metrics launch; without a native stack
+        the host path scores predict()'s float64 probabilities."""
+        from cnf_hip.metrics import CalibrationSums, calibration_record
+        stack, x, planar = self._device_stack(logits)
+        if stack is None:
+            if _on_device(logits):
+                logits = logits.detach().cpu()
+            if record is None or not record.is_cuda:
+                return super().score_sums(logits, target, bins, record)
+            # scored on the host; the caller's device record is still added to
+            if record.dtype != torch.int64 or record.shape != (4 + 3 * int(bins),):
+                raise ValueError("record must be an int64 [%d] tensor" % (4 + 3 * int(bins)))
+            host = super().score_sums(logits, target, bins).record
+            record += torch.as_tensor(host).to(record.device)
+            return CalibrationSums(record, bins)
+        y = _score_labels(target, x.device)
+        with torch.no_grad():
+            if planar:
+                return CalibrationSums(stack.score(x, self._lp_dev, y, bins, record), bins)
+            return CalibrationSums(calibration_record(stack.predict(x, self._lp_dev), y, bins,
+                                                      record), bins)
+
+    def score(self, logits, target, bins=15):
+        return self.score_sums(logits, target, bins).as_dict()
 
     def predict_logits(self, logits):
         logits = torch.as_tensor(logits, dtype=torch.float)

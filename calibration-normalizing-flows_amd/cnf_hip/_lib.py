@@ -45,7 +45,8 @@ EXPORTS = (
     "cnf_scaling_predict",
     "cnf_pav_predict",
     "cnf_planar_param_count", "cnf_planar_workspace_bytes", "cnf_planar_forward",
-    "cnf_planar_forward_loss", "cnf_planar_predict", "cnf_planar_vjp", "cnf_planar_loss_vjp",
+    "cnf_planar_forward_loss", "cnf_planar_predict", "cnf_planar_score", "cnf_planar_vjp",
+    "cnf_planar_loss_vjp",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -135,6 +136,8 @@ def _bind(lib):
                                                    P, I64, P, ctypes.c_size_t, P]),
         "cnf_planar_predict": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, I64, P,
                                               ctypes.c_size_t, P]),
+        "cnf_planar_score": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I32, P, I64, P,
+                                            ctypes.c_size_t, P]),
         "cnf_planar_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, P, P, I64, P,
                                           ctypes.c_size_t, P]),
         "cnf_planar_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, F, P, P,

@@ -77,19 +77,13 @@ def _torch_record(probs, y, bins, record):
     return record
 
 
-def calibration_record(probs, y, bins=15, record=None):
-    """ADD the calibration record of (probs [B, D], y [B]) into `record` (a
-    zeroed int64 [4 + 3 * bins] tensor on probs' device when None) and return
-    it.  A ROCm fp32 `probs` takes ONE native launch (cnf_metrics, on the
-    current stream, graph-capturable); any other tensor the torch restatement."""
+def _labels_and_record(B, dev, y, bins, record):
+    """(y, record) under the record rules every scoring call shares: int64
+    labels on `dev`, one per row, at most 2^26 rows; a zeroed record when
+    None, else a contiguous int64 [4 + 3 * bins] tensor on `dev`."""
     words = record_words(bins)
-    bins = int(bins)
-    if probs.dim() != 2 or not 2 <= probs.shape[1] <= _lib.MAX_DIM:
-        raise ValueError("probs must be [B, D] with 2 <= D <= %d" % _lib.MAX_DIM)
-    B = probs.shape[0]
     if B > MAX_ROWS:
         raise ValueError("at most 2^26 rows per call (split the batch; records add)")
-    dev = probs.device
     y = torch.as_tensor(y).to(device=dev, dtype=torch.int64).reshape(-1)
     if y.shape[0] != B:
         raise ValueError("y must hold one label per row")
@@ -98,6 +92,28 @@ def calibration_record(probs, y, bins=15, record=None):
     elif (record.dtype != torch.int64 or record.device != dev or record.numel() != words
           or not record.is_contiguous()):
         raise ValueError("record must be a contiguous int64 [%d] tensor on %s" % (words, dev))
+    return y, record
+
+
+def score_args(x, y, bins, record):
+    """(y, bins, record) of a fused score call on the [B, D] ROCm tensor x (the
+    *_score entry points, include/cnf.h), under calibration_record's rules;
+    the record is added to."""
+    y, record = _labels_and_record(x.shape[0], x.device, y, bins, record)
+    return y.contiguous(), int(bins), record
+
+
+def calibration_record(probs, y, bins=15, record=None):
+    """ADD the calibration record of (probs [B, D], y [B]) into `record` (a
+    zeroed int64 [4 + 3 * bins] tensor on probs' device when None) and return
+    it.  A ROCm fp32 `probs` takes ONE native launch (cnf_metrics, on the
+    current stream, graph-capturable); any other tensor the torch restatement."""
+    record_words(bins)  # bins in range, before anything else is looked at
+    bins = int(bins)
+    if probs.dim() != 2 or not 2 <= probs.shape[1] <= _lib.MAX_DIM:
+        raise ValueError("probs must be [B, D] with 2 <= D <= %d" % _lib.MAX_DIM)
+    B, dev = probs.shape[0], probs.device
+    y, record = _labels_and_record(B, dev, y, bins, record)
     if not (probs.is_cuda and probs.dtype == torch.float32):
         return _torch_record(probs, y, bins, record)
     probs = probs.detach().contiguous()

@@ -3,17 +3,18 @@
 `PlanarStack` binds a run of PlanarLayers of one width to the fused kernels:
 one launch for the forward + log-det (every layer's output optional), one for
 the forward + loss terms, one for the reverse mode, one for the fused
-forward + loss + reverse mode, and one for the calibrator's predict
-(`predict`: centring, the stack, both softmaxes and the prior correction,
-cnf_planar_predict).  `cnf_hip.adam.StackAdam` steps the stack's parameters
-in one launch (cnf_adam_step_tensors) from the flat gradient `loss_and_grads`
-writes, and `invalidate()` is a no-op, so the calibrator's epoch runner and
-its HIP-graph replay drive a PlanarStack as they drive a CouplingStack.  The
-layers keep owning `w`, `u`, `b`; the stack
-passes their device pointers on every call and the library re-derives `u_hat`
-inside the call, so there is no prepared state to invalidate.  Buffers are
-torch allocations on the input's device and the launches go to torch's current
-stream.
+forward + loss + reverse mode, one for the calibrator's predict (`predict`:
+centring, the stack, both softmaxes and the prior correction,
+cnf_planar_predict) and one for that predict ending in the calibration record
+instead of the probabilities (`score`, cnf_planar_score).
+`cnf_hip.adam.StackAdam` steps the stack's parameters in one launch
+(cnf_adam_step_tensors) from the flat gradient `loss_and_grads` writes, and
+`invalidate()` is a no-op, so the calibrator's epoch runner and its HIP-graph
+replay drive a PlanarStack as they drive a CouplingStack.  The layers keep
+owning `w`, `u`, `b`; the stack passes their device pointers on every call and
+the library re-derives `u_hat` inside the call, so there is no prepared state
+to invalidate.  Buffers are torch allocations on the input's device and the
+launches go to torch's current stream.
 """
 import ctypes
 
@@ -255,6 +256,29 @@ class PlanarStack:
         _lib.check("cnf_planar_predict", st)
         stats["planar_predict"] += 1
         return (probs, ld) if want_logdet else probs
+
+    def score(self, x, log_priors, y, bins=15, record=None):
+        """ADD the calibration record (cnf_hip.metrics) of predict(x,
+        log_priors) against the labels y into `record` (a zeroed int64
+        [4 + 3 * bins] tensor when None) and return it: one cnf_planar_score
+        call, the probabilities never stored.  The words are those of
+        calibration_record(predict(x, log_priors), y, bins, record)."""
+        from .metrics import score_args
+        x = self._check_input(x.detach())
+        B, dev = x.shape[0], x.device
+        lp = torch.as_tensor(log_priors, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        if lp.numel() != self.dim:
+            raise ValueError("log_priors must have %d entries" % self.dim)
+        y, bins, record = score_args(x, y, bins, record)
+        ws, n = self._ws(B, dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib().cnf_planar_score(
+                ctypes.c_int32(self.dim), ctypes.c_int32(self.L), self._ptrs(), _ptr(x), _ptr(lp),
+                _ptr(y), ctypes.c_int32(bins), _ptr(record), ctypes.c_int64(B), _ptr(ws),
+                ctypes.c_size_t(n), _stream(dev))
+        _lib.check("cnf_planar_score", st)
+        stats["planar_score"] += 1
+        return record
 
     def invalidate(self):
         """Nothing is prepared between calls (every call re-derives u_hat), so

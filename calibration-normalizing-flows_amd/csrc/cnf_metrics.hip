@@ -22,6 +22,11 @@
 // non-zero words into `record` with one integer atomic each.  The grid is at
 // most kMaxBlocks blocks, so a call issues at most kMaxBlocks * (4 + 3 * bins)
 // global atomics whatever B is.  No float atomics, no spin-wait, no workspace.
+//
+// TWIN: cnf_score.h restates Edges, the threshold loop of cnf_metrics, lds_add
+// and k_metrics' per-row and flush code for the score kernels, which must
+// leave the same words (tests/test_gpu_score.py).  A change to the bin rule,
+// the validity rules or the fixed point here belongs there too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,7 +1,8 @@
 // Planar flows (the reference's PlanarLayer, flows/flows.py:129-165) as fused
 // HIP kernels: forward + log-det (+ loss terms), and the hand-derived reverse
 // mode (+ fused loss seed), and the calibrator's predict (centring, the stack,
-// both softmaxes and the prior correction in one pass), all fp32.
+// both softmaxes and the prior correction in one pass) with its score variant
+// (the predict ending in cnf_metrics' record, cnf_score.h), all fp32.
 //
 // Rows: one lane per row for D <= 16 (the row in registers), 16 lanes per row
 // for D <= 64, 64 lanes per row above (column c of a row sits in lane c % LPR,
@@ -31,6 +32,7 @@
 #include <cstdint>
 
 #include "cnf_internal.h"
+#include "cnf_score.h"
 #include "cnf_valu_io.h"
 
 namespace cnf {
@@ -357,98 +359,21 @@ template <int LPR, int CPL>
 __global__ __launch_bounds__(kThreads) void k_planar_predict(
     const float* __restrict__ x, const float* __restrict__ blob, const float* __restrict__ lp,
     int D, int L, int cs, int64_t B, float* __restrict__ probs, float* __restrict__ ld_out) {
-  constexpr int RPB = kThreads / LPR;
-  constexpr bool kStage = LPR == 1;
-  constexpr int TS = CPL | 1;
-  __shared__ float tile[kStage ? kThreads * TS : 1];
-  const int tid = threadIdx.x, gl = tid % LPR, gi = tid / LPR;
-  float lpv[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int c = gl + LPR * k;
-    lpv[k] = c < D ? lp[c] : 0.f;
-  }
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < B; base += (int64_t)gridDim.x * RPB) {
-    const int64_t row = base + gi;
-    const bool valid = row < B;
-    const int nrows = B - base < RPB ? (int)(B - base) : RPB;
-    float xv[CPL];
-    if constexpr (kStage) {
-      const float* __restrict__ src = x + base * D;
-      for (int i = tid; i < nrows * CPL; i += kThreads) {
-        const int r = i / CPL;
-        tile[r * TS + (i - r * CPL)] = src[i];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) xv[k] = valid ? tile[tid * TS + k] : 0.f;
-      __syncthreads();
-    } else {
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int c = gl + LPR * k;
-        xv[k] = (valid && c < D) ? x[row * D + c] : 0.f;
-      }
-    }
-    // centre
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (gl + LPR * k < D) s += xv[k];
-    const float mu = row_sum<LPR>(s) / (float)D;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (gl + LPR * k < D) xv[k] -= mu;
-    float ld = 0.f;
-    for (int l = 0; l < L; ++l) planar_step<LPR, CPL>(xv, blob + (size_t)l * cs, gl, ld);
-    if (valid && ld_out && gl == 0) ld_out[row] = ld;
-    // p = softmax(z)
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (gl + LPR * k < D) m = fmaxf(m, xv[k]);
-    m = row_max<LPR>(m);
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (gl + LPR * k < D) se += expf(xv[k] - m);
-    const float lse = logf(row_sum<LPR>(se));
-    // q = log(p + 1e-7) - log_priors, probs = softmax(q)
-    float m2 = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      const float p = expf(xv[k] - m - lse);
-      xv[k] = logf(p + 1e-7f) - lpv[k];
-      if (gl + LPR * k < D) m2 = fmaxf(m2, xv[k]);
-    }
-    m2 = row_max<LPR>(m2);
-    float s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      xv[k] = expf(xv[k] - m2);
-      if (gl + LPR * k < D) s2 += xv[k];
-    }
-    s2 = row_sum<LPR>(s2);
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) xv[k] = xv[k] / s2;
-    if constexpr (kStage) {
-      float* __restrict__ dst = probs + base * D;
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) tile[tid * TS + k] = xv[k];
-      __syncthreads();
-      for (int i = tid; i < nrows * CPL; i += kThreads) {
-        const int r = i / CPL;
-        dst[i] = tile[r * TS + (i - r * CPL)];
-      }
-      __syncthreads();
-    } else if (valid) {
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) {
-        const int c = gl + LPR * k;
-        if (c < D) probs[row * D + c] = xv[k];
-      }
-    }
-  }
+#define CNF_SCORE 0
+#include "cnf_planar_predict.inc"
+#undef CNF_SCORE
+}
+
+// k_planar_predict with the scoring epilogue (cnf_score.h) in place of the
+// store phase; the log-det is not written
+template <int LPR, int CPL>
+__global__ __launch_bounds__(kThreads) void k_planar_score(
+    const float* __restrict__ x, const float* __restrict__ blob, const float* __restrict__ lp,
+    int D, int L, int cs, int64_t B, score::Args sc) {
+  __shared__ long long rec[score::kRecWords];
+#define CNF_SCORE 1
+#include "cnf_planar_predict.inc"
+#undef CNF_SCORE
 }
 
 // ---- reverse mode -------------------------------------------------------------
@@ -782,6 +707,13 @@ void launch_predict(int blocks, hipStream_t s, const float* x, const float* blob
 }
 
 template <int LPR, int CPL>
+void launch_score(int blocks, hipStream_t s, const float* x, const float* blob, const float* lp,
+                  int D, int L, int cs, int64_t B, const score::Args& sc) {
+  hipLaunchKernelGGL((k_planar_score<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, lp, D,
+                     L, cs, B, sc);
+}
+
+template <int LPR, int CPL>
 void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
   if (a.L > kRegL) {
     hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
@@ -911,6 +843,29 @@ int run_predict(int32_t D, int32_t L, const float* const* params, const float* x
   return hip_status(hipGetLastError());
 }
 
+int run_score(int32_t D, int32_t L, const float* const* params, const float* x, const float* lp,
+              const int64_t* y, int32_t bins, int64_t* record, int64_t B, void* ws, size_t ws_bytes,
+              hipStream_t s) {
+  Ptrs P;
+  Geo g;
+  Plan p;
+  int st = check_shape(D, L);
+  if (st != CNF_OK) return st;
+  st = score::check_args(D, bins, B, y, record);
+  if (st != CNF_OK) return st;
+  st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
+  if (st != CNF_OK) return st;
+  if (B > 0 && !lp) return CNF_ERR_NULL;
+  if (mis4(lp)) return CNF_ERR_ALIGN;
+  if (B == 0) return CNF_OK;
+  float* w = static_cast<float*>(ws);
+  st = run_prep(P, g, D, L, w + p.blob, s);
+  if (st != CNF_OK) return st;
+  const score::Args sc = score::make_args(y, bins, record);
+  CNF_PLANAR_DISPATCH(launch_score, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, sc);
+  return hip_status(hipGetLastError());
+}
+
 int run_backward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
                  int32_t kind, float det, float gscale, const float* gz, const float* gz_all,
                  const float* gld, float* terms, float* grads, float* dx, int64_t B, void* ws,
@@ -1022,6 +977,15 @@ extern "C" int cnf_planar_predict(int32_t dim, int32_t n_layers, const float* co
   CNF_RANGE("cnf_planar_predict");
   return cnf::run_predict(dim, n_layers, params, x, log_priors, probs, logdet, B, workspace,
                           workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int cnf_planar_score(int32_t dim, int32_t n_layers, const float* const* params,
+                                const float* x, const float* log_priors, const int64_t* y,
+                                int32_t bins, int64_t* record, int64_t B, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  CNF_RANGE("cnf_planar_score");
+  return cnf::run_score(dim, n_layers, params, x, log_priors, y, bins, record, B, workspace,
+                        workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int cnf_planar_vjp(int32_t dim, int32_t n_layers, const float* const* params,

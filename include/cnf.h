@@ -427,6 +427,23 @@ int cnf_planar_forward_loss(int32_t dim, int32_t n_layers, const float* const* p
 int cnf_planar_predict(int32_t dim, int32_t n_layers, const float* const* params,
                        const float* x, const float* log_priors, float* probs, float* logdet,
                        int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+/* The score variant of cnf_planar_predict: ONE launch that runs the predict
+ * arithmetic up to the fp32 probability it would store and, instead of storing
+ * it, ADDS the row into `record` exactly as cnf_metrics would from the stored
+ * matrix -- the record layout, validity rules, bin thresholds and add-into
+ * contract documented at cnf_metrics -- so
+ *   cnf_planar_score(x, ..., y, bins, record)
+ * leaves the words of cnf_planar_predict(x, ..., probs) followed by
+ * cnf_metrics(probs, y, ...) without the [B][D] matrix going to memory (the
+ * log-det is not produced).  y: [B] int64 DEVICE labels.  Grid, rows per
+ * block, workspace and prepare launch are the sibling's.  Validation is the
+ * sibling's plus cnf_metrics': 2 <= dim, bins in 1..CNF_MAX_BINS
+ * (CNF_ERR_DESC), B <= 2^26 (CNF_ERR_BATCH), y and record 8-byte aligned
+ * (CNF_ERR_ALIGN), record non-NULL; all before any HIP call.  B == 0 returns
+ * CNF_OK without a launch and leaves the record as it is. */
+int cnf_planar_score(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                     const float* log_priors, const int64_t* y, int32_t bins, int64_t* record,
+                     int64_t B, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Reverse mode of cnf_planar_forward, as cnf_vjp: upstream gz [B][D], gz_all
  * [L][B][D], gld [B] (each may be NULL = zero); writes grads
