@@ -18,6 +18,11 @@ cnf_planar_loss_vjp.  `predict` / `evaluate` / `detection_curves` of a planar
 calibrator on a ROCm device are one cnf_planar_predict launch on a resident
 replica, and `evaluate` copies only the 4 + 3 * bins record words to the host.
 CNF_PLANAR_NATIVE=0 keeps a planar flow on torch ops throughout.
+A flow made of RadialLayers (flows._factory.RadialFlow) takes the same route
+on the cnf_radial_* kernels -- cnf_radial_loss_vjp, cnf_radial_forward_loss,
+cnf_radial_predict, cnf_radial_score; its `history['log_det']` is zeros, the
+layer's log-det being the reference's constant 0 -- and CNF_RADIAL_NATIVE=0
+keeps it on torch ops.
 Any other flow (or a CPU device) runs the reference's own torch loop.
 
 The scaling baselines -- TempScalingCalibrator, MLRCalibrator,
@@ -39,8 +44,8 @@ per-class tables and returns a ROCm fp32 tensor.  (The fit itself is not on
 the device yet: DESIGN.md section 7d.)
 
 `Calibrator.score` / `score_sums` is the one scoring interface of every
-calibrator.  A planar TorchFlowCalibrator scores in ONE fused launch that never
-stores the probabilities (cnf_planar_score).  DummyCalibrator (whose predict
+calibrator.  A planar or radial TorchFlowCalibrator scores in ONE fused launch
+that never stores the probabilities (cnf_planar_score, cnf_radial_score).  DummyCalibrator (whose predict
 now also runs on the device), the four scaling calibrators, PAVCalibrator and
 a coupling flow score a ROCm tensor with their fused predict plus one
 cnf_metrics launch; host inputs go through predict() and the record of
@@ -485,6 +490,40 @@ def _planar_stack(flow, dev):
     return flow._planar_stack()
 
 
+def _radial_stack(flow, dev):
+    """The fused RadialStack behind `flow`, or None when the flow is not an
+    all-radial Flow with fp32 parameters on the ROCm device `dev`, the shape is
+    outside the kernels' envelope, or CNF_RADIAL_NATIVE=0."""
+    if torch.device(dev).type != "cuda":
+        return None
+    try:
+        from flows import flows as F
+        from cnf_hip import _lib
+        from cnf_hip.radial import RadialStack
+    except ImportError:
+        return None
+    if not F.RADIAL_NATIVE or not isinstance(flow, F.Flow):
+        return None
+    layers = list(flow.layers)
+    if not layers or not all(isinstance(l, F.RadialLayer) for l in layers):
+        return None
+    ps = [p for l in layers for p in (l.z0, l.a, l.b)]
+    if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
+        return None
+    if not RadialStack.compatible(layers, ps[0].device):
+        return None
+    if not (1 <= layers[0].z0.numel() <= _lib.MAX_DIM and len(layers) <= _lib.RADIAL_MAX_LAYERS):
+        return None
+    return flow._radial_stack()
+
+
+def _tensor_stack(flow, dev):
+    """The PlanarStack or RadialStack behind `flow` (the stacks without a
+    cnf_desc, whose parameters StackAdam steps as a tensor list), or None."""
+    stack = _planar_stack(flow, dev)
+    return stack if stack is not None else _radial_stack(flow, dev)
+
+
 def _loader_order(n):
     """The row order of one pass of DataLoader(TensorDataset(...), batch_size,
     shuffle=True) (calibrators.py:274-275) with torch's global CPU RNG in the
@@ -508,7 +547,7 @@ class _EpochRunner:
     eval pass's fused forward + loss per batch, whose LAST batch's sums are the
     epoch's history terms.
 
-    `stack` is a CouplingStack or a PlanarStack; the runner uses
+    `stack` is a CouplingStack, a PlanarStack or a RadialStack; the runner uses
     loss_and_grads(x, y, grad_scale=, grads_out=, terms_out=),
     forward_loss(x, y, terms_out=), reserve_workspace / release_workspace and
     invalidate() (no-ops where a stack has nothing to do).  The flat gradient
@@ -624,12 +663,12 @@ class TorchFlowCalibrator(Calibrator):
             # that the calibrator's `dev`, which need not be the current GPU
             with torch.cuda.device(logits.device):
                 history = self._fit_native(stack, logits, target, epochs, batch_size)
-        elif _planar_stack(self.flow, self.dev) is not None:
+        elif _tensor_stack(self.flow, self.dev) is not None:
             from cnf_hip import adam
-            pstack = _planar_stack(self.flow, self.dev)
-            fit = self._fit_native if adam.supports(self.optimizer) else self._fit_planar
+            tstack = _tensor_stack(self.flow, self.dev)
+            fit = self._fit_native if adam.supports(self.optimizer) else self._fit_torch_step
             with torch.cuda.device(logits.device):
-                history = fit(pstack, logits, target, epochs, batch_size)
+                history = fit(tstack, logits, target, epochs, batch_size)
         else:
             history = self._fit_torch(logits, target, epochs, batch_size)
         self.flow.cpu()
@@ -676,7 +715,8 @@ class TorchFlowCalibrator(Calibrator):
         """Same schedule on the fused kernels: one cnf_loss_vjp launch plus one
         cnf_adam_step launch per training batch, one cnf_forward_loss launch per
         evaluation batch (a PlanarStack: cnf_planar_loss_vjp,
-        cnf_adam_step_tensors, cnf_planar_forward_loss).  Each pass over the
+        cnf_adam_step_tensors, cnf_planar_forward_loss; a RadialStack: the
+        cnf_radial_* siblings).  Each pass over the
         data draws its order exactly as
         the reference's DataLoader(shuffle=True) does (_loader_order), so
         minibatch runs see the reference's batches and the eval history keeps
@@ -712,13 +752,14 @@ class TorchFlowCalibrator(Calibrator):
         return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
                 'log_det': list(hist[:, 2].unbind(0))}
 
-    def _fit_planar(self, stack, logits, target, epochs, batch_size):
-        """The planar fit under an optimizer the native Adam does not reproduce
-        (cnf_hip.adam.supports is false: AdamW, amsgrad, ...), every epoch
-        eager: per training batch one cnf_planar_loss_vjp launch whose flat
-        gradient is viewed into each parameter's .grad, then the torch
+    def _fit_torch_step(self, stack, logits, target, epochs, batch_size):
+        """The fit of a planar or radial stack under an optimizer the native
+        Adam does not reproduce (cnf_hip.adam.supports is false: AdamW,
+        amsgrad, ...), every epoch eager: per training batch one fused loss +
+        reverse-mode launch (cnf_planar_loss_vjp / cnf_radial_loss_vjp) whose
+        flat gradient is viewed into each parameter's .grad, then the torch
         optimizer's own step (its state stays torch's); per evaluation batch
-        one cnf_planar_forward_loss launch.  Every pass draws its order as the
+        one fused forward + loss launch.  Every pass draws its order as the
         reference's DataLoader(shuffle=True) does (_loader_order), and the history keeps
         the last batch's sums over N (calibrators.py:274-317)."""
         N = logits.shape[0]
@@ -763,16 +804,16 @@ class TorchFlowCalibrator(Calibrator):
         return self._replica[1]
 
     def _device_stack(self, logits):
-        """(stack, x, planar): the native stack of the resident replica, the
-        logits as an fp32 tensor on self.dev and whether the stack is a
-        PlanarStack; (None, None, False) when no native stack serves this flow
-        there."""
+        """(stack, x, fused_score): the native stack of the resident replica,
+        the logits as an fp32 tensor on self.dev and whether the stack has a
+        one-launch score (a PlanarStack or RadialStack); (None, None, False)
+        when no native stack serves this flow there."""
         if torch.device(self.dev).type != "cuda":
             return None, None, False
         flow = self._device_flow()
-        stack, planar = _native_stack(flow, self.dev, need_vjp=False), False
+        stack, fused_score = _native_stack(flow, self.dev, need_vjp=False), False
         if stack is None:
-            stack, planar = _planar_stack(flow, self.dev), True
+            stack, fused_score = _tensor_stack(flow, self.dev), True
         if stack is None:
             return None, None, False
         if _on_device(logits):
@@ -781,7 +822,7 @@ class TorchFlowCalibrator(Calibrator):
             x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
         if self._lp_dev is None:
             self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float, device=self.dev)
-        return stack, x, planar
+        return stack, x, fused_score
 
     def _predict_device(self, logits):
         """predict()'s fp32 probabilities as a tensor on self.dev, or None when
@@ -796,7 +837,8 @@ class TorchFlowCalibrator(Calibrator):
         """Calibrator.predict (calibrators.py:40-44 with predict_post, :330-353):
         centring, the flow, softmax and the prior correction
         softmax(log(p + 1e-7) - log_priors).  On a ROCm device this is ONE fused
-        launch (cnf_predict; cnf_planar_predict for a planar flow) on a
+        launch (cnf_predict; cnf_planar_predict / cnf_radial_predict for a
+        planar / radial flow) on a
         resident replica of the flow, with one H2D copy of the logits and one
         D2H copy of the probabilities."""
         probs = self._predict_device(logits)
@@ -827,12 +869,13 @@ class TorchFlowCalibrator(Calibrator):
 
     def score_sums(self, logits, target, bins=15, record=None):
         """evaluate_sums' record (logits: arrays or tensors, ROCm ones
-        included).  A planar flow on a ROCm device scores in ONE
-        cnf_planar_score launch on the resident replica; a coupling flow keeps
+        included).  A planar or radial flow on a ROCm device scores in ONE
+        cnf_planar_score / cnf_radial_score launch on the resident replica; a
+        coupling flow keeps
         its fused predict plus one cnf_metrics launch; without a native stack
         the host path scores predict()'s float64 probabilities."""
         from cnf_hip.metrics import CalibrationSums, calibration_record
-        stack, x, planar = self._device_stack(logits)
+        stack, x, fused_score = self._device_stack(logits)
         if stack is None:
             if _on_device(logits):
                 logits = logits.detach().cpu()
@@ -846,7 +889,7 @@ class TorchFlowCalibrator(Calibrator):
             return CalibrationSums(record, bins)
         y = _score_labels(target, x.device)
         with torch.no_grad():
-            if planar:
+            if fused_score:
                 return CalibrationSums(stack.score(x, self._lp_dev, y, bins, record), bins)
             return CalibrationSums(calibration_record(stack.predict(x, self._lp_dev), y, bins,
                                                       record), bins)

@@ -32,6 +32,8 @@ SCALE_FULL_MAX_DIM = 128
 PAV_LDS_ENTRIES = 2048  # cnf_pav_predict stages the tables in LDS when D * cap <= this
 PLANAR_MAX_LAYERS = 64  # CNF_PLANAR_MAX_LAYERS (cnf_planar_*)
 PLANAR_REG_LAYERS = 10  # deeper stacks keep their tanh tape in the workspace
+RADIAL_MAX_LAYERS = 64  # CNF_RADIAL_MAX_LAYERS (cnf_radial_*)
+RADIAL_REG_LAYERS = 10  # deeper stacks keep their tape of r in the workspace
 
 # Every symbol include/cnf.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -47,6 +49,9 @@ EXPORTS = (
     "cnf_planar_param_count", "cnf_planar_workspace_bytes", "cnf_planar_forward",
     "cnf_planar_forward_loss", "cnf_planar_predict", "cnf_planar_score", "cnf_planar_vjp",
     "cnf_planar_loss_vjp",
+    "cnf_radial_param_count", "cnf_radial_workspace_bytes", "cnf_radial_forward",
+    "cnf_radial_forward_loss", "cnf_radial_predict", "cnf_radial_score", "cnf_radial_vjp",
+    "cnf_radial_loss_vjp",
     "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -142,6 +147,21 @@ def _bind(lib):
                                           ctypes.c_size_t, P]),
         "cnf_planar_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, F, P, P,
                                                P, I64, P, ctypes.c_size_t, P]),
+        "cnf_radial_param_count": (ctypes.c_int, [I32, I32, ctypes.POINTER(I64)]),
+        "cnf_radial_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
+                                                      ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_radial_forward": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
+        "cnf_radial_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, P, P,
+                                                   I64, P, ctypes.c_size_t, P]),
+        "cnf_radial_predict": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
+        "cnf_radial_score": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I32, P, I64, P,
+                                            ctypes.c_size_t, P]),
+        "cnf_radial_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, P, I64, P,
+                                          ctypes.c_size_t, P]),
+        "cnf_radial_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P, P,
+                                               I64, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),

@@ -25,7 +25,9 @@ from . import _lib
 # counts the launches that went through the torch.library operators
 stats = {"forward": 0, "inverse": 0, "prepare": 0, "vjp": 0, "loss_vjp": 0, "predict": 0,
          "metrics": 0, "torch_ops": 0, "planar_forward": 0, "planar_vjp": 0,
-         "planar_loss_vjp": 0, "planar_predict": 0, "planar_score": 0}
+         "planar_loss_vjp": 0, "planar_predict": 0, "planar_score": 0,
+         "radial_forward": 0, "radial_vjp": 0, "radial_loss_vjp": 0, "radial_predict": 0,
+         "radial_score": 0}
 
 # Dispatch through torch.ops.cnf (C++ operators, autograd in C++) when
 # libcnf_torch.so is built; False: the ctypes calls of the same C ABI.

@@ -7,8 +7,14 @@ not the reference Flow's list.  The reference notebooks import such factories
 from `flows.realNVP_torch` / `flows.nice_torch`, modules absent from the
 reference repo; their defaults here follow code-old/realNVP.py:46-52
 (layers=4, hidden_size=[dim]) and are otherwise unpinned.
+
+PlanarFlow, RadialFlow and AffineConstantFlow are what the calibration
+notebooks import from `flows.normalizing_flows_torch` (re-exported there),
+another module absent from the reference repo, so their defaults are unpinned
+too: layers=10 is the notebooks' planar / radial depth, layers=5 the
+AffineConstantFlow depth of train-flows-det.ipynb.
 """
-from .flows import Flow, NvpCouplingLayer, PlanarLayer
+from .flows import AffineConstantLayer, Flow, NvpCouplingLayer, PlanarLayer, RadialLayer
 
 
 class CouplingFlow(Flow):
@@ -45,6 +51,42 @@ class PlanarFlow(Flow):
 
     def forward(self, x):
         return self.transform(x)
+
+    def forward_all(self, x):
+        """The reference Flow.forward: (zs list, cum_log_det)."""
+        return Flow.forward(self, x)
+
+
+class RadialFlow(Flow):
+    """A Flow of RadialLayers whose call returns (z_final, log_det), the
+    log-det being the reference's constant 0-d zero; layers=10 as the planar
+    factory."""
+
+    def __init__(self, dim, layers=10, **kwargs):
+        super().__init__([RadialLayer(dim) for _ in range(layers)])
+        self.dim = dim
+
+    def forward(self, x):
+        return self.transform(x)
+
+    def forward_all(self, x):
+        """The reference Flow.forward: (zs list, cum_log_det)."""
+        return Flow.forward(self, x)
+
+
+class AffineConstantFlow(Flow):
+    """A Flow of AffineConstantLayers (z = x * exp(s) + t per layer) whose call
+    returns (z_final, log_det).  Torch ops on every device."""
+
+    def __init__(self, dim, layers=5, **kwargs):
+        super().__init__([AffineConstantLayer(dim) for _ in range(layers)])
+        self.dim = dim
+
+    def forward(self, x):
+        return self.transform(x)
+
+    def backward(self, z):
+        return self.inverse_transform(z)
 
     def forward_all(self, x):
         """The reference Flow.forward: (zs list, cum_log_det)."""

@@ -5,8 +5,8 @@ conventions as the reference (SergioAlvarezB/calibration-normalizing-flows,
 flows/flows.py), so `from flows.flows import Flow, NvpCouplingLayer` works
 unchanged.  On a ROCm device a Flow made of NvpCouplingLayers runs as ONE fused
 HIP launch per call (libcnf_hip.so, include/cnf.h), and so does a Flow made of
-PlanarLayers (cnf_planar_*; forward only, the planar flow has no tractable
-inverse):
+PlanarLayers (cnf_planar_*) or of RadialLayers (cnf_radial_*; both forward
+only, neither flow has a tractable inverse):
 
   Flow.forward(x)  -> (zs, cum_log_det)   fused cnf_forward, zs = views of one
                                            [L, B, D] buffer       (flows.py:17-25)
@@ -17,14 +17,18 @@ inverse):
 from torch autograd, which calls the native VJP kernel.
 
 Host tensors (CPU) run the same math with torch ops, as the reference does.
-Layers the native engine does not cover (AffineConstantLayer, RadialLayer --
-out of the hot-path scope) and mixed stacks run as torch ops, layer
-by layer.  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops as well.
+Layers the native engine does not cover (AffineConstantLayer -- out of the
+hot-path scope) and mixed stacks run as torch ops, layer by layer.
+CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops as well, and
+CNF_RADIAL_NATIVE=0 radial ones.  A radial stack's log-det is the reference's
+constant log(1) = 0: the native path returns the same 0-d fp32 zero.
 
-A planar stack's other launches hang off the same binding (cnf_hip/planar.py):
-the fused training step and loss evaluation, the calibrator's fused predict
-(cnf_planar_predict) and the one-launch Adam step (cnf_adam_step_tensors);
-calibrators.TorchFlowCalibrator drives them, HIP-graph epoch replay included.
+A planar or radial stack's other launches hang off the same kind of binding
+(cnf_hip/planar.py, cnf_hip/radial.py): the fused training step and loss
+evaluation, the calibrator's fused predict and score (cnf_planar_predict,
+cnf_radial_predict, ..._score) and the one-launch Adam step
+(cnf_adam_step_tensors); calibrators.TorchFlowCalibrator drives them, HIP-graph
+epoch replay included.
 """
 import os
 import warnings
@@ -47,6 +51,9 @@ STRICT_NATIVE = os.environ.get("CNF_STRICT_NATIVE", "0") == "1"
 # CNF_PLANAR_NATIVE=0: planar flows on a ROCm device stay on the torch ops
 # (the baseline of tools/planar_bench.py).
 PLANAR_NATIVE = os.environ.get("CNF_PLANAR_NATIVE", "1") != "0"
+# CNF_RADIAL_NATIVE=0: the same for radial flows (the baseline of
+# tools/radial_bench.py).
+RADIAL_NATIVE = os.environ.get("CNF_RADIAL_NATIVE", "1") != "0"
 
 _warned = set()
 
@@ -118,6 +125,36 @@ def _planar_run(stack, x, want_all):
         return None
 
 
+def _radial_eligible(layers, x):
+    """True when these layers can run as one fused radial stack on x."""
+    if not RADIAL_NATIVE or not (isinstance(x, torch.Tensor) and x.is_cuda):
+        return False
+    if x.dtype != torch.float32 or x.dim() != 2:
+        return False
+    if not layers or not all(isinstance(ly, RadialLayer) for ly in layers):
+        return False
+    from cnf_hip.radial import RadialStack
+    if not RadialStack.compatible(layers, x.device):
+        return False
+    return x.shape[1] == layers[0].z0.numel()
+
+
+def _radial_run(stack, x, want_all):
+    """(zs list | final z, the 0-d zero log-det) of a RadialStack, or None when
+    the shape is outside the kernels' envelope."""
+    from cnf_hip._lib import UnsupportedShape
+    try:
+        if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
+            out, ld = stack.forward_autograd(x, want_all=want_all)
+        else:
+            fin, ld, allt = stack.run(x, want_all=want_all)
+            out = allt if want_all else fin
+        return (list(out.unbind(0)) if want_all else out), ld
+    except UnsupportedShape as e:
+        _not_native(str(e))
+        return None
+
+
 def _squeeze_ld(ld):
     # torch.sum(..., dim=1).squeeze(): 0-d for a single row (flows/flows.py:109)
     return ld.squeeze()
@@ -139,6 +176,8 @@ class Flow(nn.Module):
         self._stack_key = None
         self._pstack = None
         self._pstack_key = None
+        self._rstack = None
+        self._rstack_key = None
 
     def __getstate__(self):
         # the native binding (ctypes descriptor, device blobs) is rebuilt lazily
@@ -147,6 +186,8 @@ class Flow(nn.Module):
         st["_stack_key"] = None
         st["_pstack"] = None
         st["_pstack_key"] = None
+        st["_rstack"] = None
+        st["_rstack_key"] = None
         return st
 
     # -- native plumbing --------------------------------------------------
@@ -167,6 +208,14 @@ class Flow(nn.Module):
             self._pstack_key = key
         return self._pstack
 
+    def _radial_stack(self):
+        key = tuple((id(ly), id(ly.z0), id(ly.a), id(ly.b)) for ly in self.layers)
+        if getattr(self, "_rstack", None) is None or self._rstack_key != key:
+            from cnf_hip.radial import RadialStack
+            self._rstack = RadialStack(list(self.layers))
+            self._rstack_key = key
+        return self._rstack
+
     def invalidate_native(self):
         """Drop the native binding's prepared weights.  Needed only after writes
         that bypass torch's version counters (`p.data.copy_(...)`); optimizer
@@ -175,6 +224,8 @@ class Flow(nn.Module):
         self._stack_key = None
         self._pstack = None
         self._pstack_key = None
+        self._rstack = None
+        self._rstack_key = None
         for ly in self.layers:
             if isinstance(ly, NvpCouplingLayer):
                 ly._stack = None
@@ -188,6 +239,9 @@ class Flow(nn.Module):
         if not inverse and layers and isinstance(layers[0], PlanarLayer) \
                 and _planar_eligible(layers, x):
             return _planar_run(self._planar_stack(), x, want_all)
+        if not inverse and layers and isinstance(layers[0], RadialLayer) \
+                and _radial_eligible(layers, x):
+            return _radial_run(self._radial_stack(), x, want_all)
         if not _native_eligible(layers, x):
             return None
         from cnf_hip._lib import UnsupportedShape
@@ -416,7 +470,8 @@ class PlanarLayer(nn.Module):
 
 class RadialLayer(nn.Module):
     """Radial flow (reference flows/flows.py:168-193); non-invertible.  Its
-    log-det is the constant log(1) = 0, as in the reference."""
+    log-det is the constant log(1) = 0, as in the reference.  On a ROCm device
+    one fused launch (cnf_radial_forward, L = 1); torch ops on the host."""
 
     def __init__(self, dim):
         super().__init__()
@@ -424,8 +479,27 @@ class RadialLayer(nn.Module):
         self.a = nn.Parameter(torch.rand(1))
         self.b = nn.Parameter(torch.rand(1))
         self.invertible = False
+        self._stack = None
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_stack"] = None
+        return st
+
+    def _native(self, x):
+        if not _radial_eligible([self], x):
+            return None
+        st = getattr(self, "_stack", None)
+        if st is None or st.param_tensors()[0] is not self.z0 \
+                or st.param_tensors()[1] is not self.a or st.param_tensors()[2] is not self.b:
+            from cnf_hip.radial import RadialStack
+            st = self._stack = RadialStack([self])
+        return _radial_run(st, x, want_all=False)
 
     def forward(self, x):
+        out = self._native(x)
+        if out is not None:
+            return out
         b_hat = -self.a + torch.log1p(torch.exp(self.b))
         diff = x - self.z0
         h = 1. / (self.a + torch.norm(diff, dim=1, keepdim=True))

@@ -462,6 +462,97 @@ int cnf_planar_loss_vjp(int32_t dim, int32_t n_layers, const float* const* param
                         float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Radial flows: a Flow of the reference's RadialLayers (flows/flows.py:168-193;
+ * the radial calibrator of the calibration notebooks).  Per layer, with
+ * parameters z0 [D], a [1], b [1] (that state_dict order):
+ *   sp = log1p(exp(b)),  beta = -a + sp
+ *   d = x - z0,  r = ||d||_2,  h = 1 / (a + r),  z = x + beta * h * d
+ * The layer's log-det is the reference's constant log(1.0) = 0 (a quirk, kept):
+ * no entry point takes or produces a log-det, and the third loss term is 0.
+ * IEEE division and square root; a + r == 0 gives h = inf and a row with
+ * r == 0 there becomes NaN, as in the reference.  All fp32.
+ *   dim       D, 1..CNF_MAX_DIM;  n_layers  L, 1..CNF_RADIAL_MAX_LAYERS
+ *             (< 1: CNF_ERR_DESC; above: CNF_ERR_UNSUPPORTED)
+ *   params    HOST array of 3 * L DEVICE pointers: z0, a, b of layer 0, 1, ...
+ *   B         0..2^31 rows (CNF_ERR_BATCH otherwise)
+ *   workspace cnf_radial_workspace_bytes(dim, n_layers, B) bytes of DEVICE
+ *             memory, no initialisation needed; one size serves every entry
+ *             point.  A call first writes each layer's (z0, a, sp, beta,
+ *             sigmoid(b)) there with one small launch, which every kernel of
+ *             the call reads, so nothing is cached between calls.
+ * In floats, with LPR = 1 (D <= 16), 16 (D <= 64) or 64 lanes per row,
+ * DP = D rounded up to a multiple of LPR, PW = L * (D + 2) + 4 and r64(n) = n
+ * rounded up to a multiple of 64, the workspace holds
+ *   r64(L * (DP + 8)) + r64(PW) + r64(max(U * PW, 4 * F)) + (L > 10 ? r64(L * B) : 0)
+ * where F = min(1024, ceil(B * LPR / 256)) blocks of the forward grid (at
+ * least 1) and U the records of the reverse grid: C = min(256, ceil(B * LPR /
+ * 256)) blocks when PW <= 3072, else 4 records for each of min(C, max(4,
+ * 2^20 / PW)) blocks.  The last term is the per-(row, layer) tape of r for
+ * stacks deeper than 10 layers (shallower ones keep it in registers).
+ * Argument errors (NULL, alignment, shape, batch) are returned before any
+ * launch; B == 0 zeroes loss_terms / grads with memset nodes and launches no
+ * kernel.  Deterministic: per-block partial sums added in block order by a
+ * one-block follow-up launch; the grids depend on (D, L, B) only, so two calls
+ * agree bitwise.  No float atomics, no allocation, no host synchronisation. */
+#define CNF_RADIAL_MAX_LAYERS 64
+
+/* 3 * L tensors, L * (D + 2) floats. */
+int cnf_radial_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats);
+int cnf_radial_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B, size_t* bytes);
+
+/* Flow.forward of the stack: z [B][D] (= zs[-1]) and z_all [L][B][D] (the zs
+ * list); each may be NULL. */
+int cnf_radial_forward(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, float* z, float* z_all, int64_t B, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* Forward + loss terms: loss_terms[3] = {sum of per-row loss, sum of ce, 0}
+ * for CNF_LOSS_CAL (ce = -log(softmax(z)[y] + 1e-7)) / CNF_LOSS_CE
+ * (ce = -log softmax(z)[y]); the log-det being 0, loss == ce and there is no
+ * `det` weight.  z may be NULL.  A label outside [0, D) makes the terms NaN. */
+int cnf_radial_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
+                            const float* x, const int64_t* y, int32_t loss_kind, float* z,
+                            float* loss_terms, int64_t B, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* Calibrator.predict of a radial flow calibrator, per row:
+ *   xc = x - mean(x);  z = radial stack(xc);  p = softmax(z)
+ *   probs = softmax(log(p + 1e-7) - log_priors)
+ * in one pass that keeps the row in registers.  log_priors [D] DEVICE floats;
+ * probs [B][D].  Envelope, workspace, prepare launch, validation, B == 0 rule
+ * and determinism as cnf_radial_forward. */
+int cnf_radial_predict(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, const float* log_priors, float* probs, int64_t B,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* The score variant of cnf_radial_predict, as cnf_planar_score is of
+ * cnf_planar_predict: ONE launch that ADDS into `record` the words that
+ * cnf_radial_predict followed by cnf_metrics(probs, y, ...) would leave; the
+ * probabilities are never stored.  Validation is the sibling's plus
+ * cnf_metrics' (2 <= dim, bins in 1..CNF_MAX_BINS, B <= 2^26, y and record
+ * 8-byte aligned, record non-NULL), all before any HIP call.  B == 0 returns
+ * CNF_OK without a launch and leaves the record as it is. */
+int cnf_radial_score(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                     const float* log_priors, const int64_t* y, int32_t bins, int64_t* record,
+                     int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Reverse mode of cnf_radial_forward: upstream gz [B][D], gz_all [L][B][D]
+ * (each may be NULL = zero); writes grads [cnf_radial_param_count] (per layer
+ * z0, a, b; overwritten) and dx [B][D] (may be NULL).  The forward pass is
+ * recomputed inside; the only tape is one r per (row, layer), from which a
+ * layer's input is rebuilt as z0 + (z - z0) (a + r) / (r + sp).  The norm's
+ * gradient is 0 where r == 0, as torch's. */
+int cnf_radial_vjp(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                   const float* gz, const float* gz_all, float* grads, float* dx, int64_t B,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fused forward + loss + reverse mode, as cnf_planar_loss_vjp without `det`:
+ * loss_terms[3] (sums over this batch, the third 0), grads = grad_scale *
+ * d(sum of the per-row loss)/d(params), dx [B][D] likewise, may be NULL. */
+int cnf_radial_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
+                        const float* x, const int64_t* y, int32_t loss_kind, float grad_scale,
+                        float* loss_terms, float* grads, float* dx, int64_t B, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"

@@ -132,7 +132,7 @@ def bench_fit_epoch(D, L, N):
             run.eager_epoch(terms[0])
 
     times = alternate({"graph": lambda: graph.replay(terms), "eager": eager,
-                       "parent_loop": lambda: cal._fit_planar(stack, xs, ys, a.reps, N)},
+                       "parent_loop": lambda: cal._fit_torch_step(stack, xs, ys, a.reps, N)},
                       per_call=a.reps)
     stack.release_workspace()
     assert bool(torch.isfinite(terms).all())
