@@ -463,65 +463,38 @@ def _native_stack(flow, dev, need_vjp=True):
     return stack if st == 0 else None
 
 
-def _planar_stack(flow, dev):
-    """The fused PlanarStack behind `flow`, or None when the flow is not an
-    all-planar Flow with fp32 parameters on the ROCm device `dev`, the shape is
-    outside the kernels' envelope, or CNF_PLANAR_NATIVE=0."""
-    if torch.device(dev).type != "cuda":
-        return None
-    try:
-        from flows import flows as F
-        from cnf_hip import _lib
-        from cnf_hip.planar import PlanarStack
-    except ImportError:
-        return None
-    if not F.PLANAR_NATIVE or not isinstance(flow, F.Flow):
-        return None
-    layers = list(flow.layers)
-    if not layers or not all(isinstance(l, F.PlanarLayer) for l in layers):
-        return None
-    ps = [p for l in layers for p in (l.w, l.u, l.b)]
-    if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
-        return None
-    if not PlanarStack.compatible(layers, ps[0].device):
-        return None
-    if not (1 <= layers[0].w.numel() <= _lib.MAX_DIM and len(layers) <= _lib.PLANAR_MAX_LAYERS):
-        return None
-    return flow._planar_stack()
-
-
-def _radial_stack(flow, dev):
-    """The fused RadialStack behind `flow`, or None when the flow is not an
-    all-radial Flow with fp32 parameters on the ROCm device `dev`, the shape is
-    outside the kernels' envelope, or CNF_RADIAL_NATIVE=0."""
-    if torch.device(dev).type != "cuda":
-        return None
-    try:
-        from flows import flows as F
-        from cnf_hip import _lib
-        from cnf_hip.radial import RadialStack
-    except ImportError:
-        return None
-    if not F.RADIAL_NATIVE or not isinstance(flow, F.Flow):
-        return None
-    layers = list(flow.layers)
-    if not layers or not all(isinstance(l, F.RadialLayer) for l in layers):
-        return None
-    ps = [p for l in layers for p in (l.z0, l.a, l.b)]
-    if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
-        return None
-    if not RadialStack.compatible(layers, ps[0].device):
-        return None
-    if not (1 <= layers[0].z0.numel() <= _lib.MAX_DIM and len(layers) <= _lib.RADIAL_MAX_LAYERS):
-        return None
-    return flow._radial_stack()
-
-
 def _tensor_stack(flow, dev):
-    """The PlanarStack or RadialStack behind `flow` (the stacks without a
-    cnf_desc, whose parameters StackAdam steps as a tensor list), or None."""
-    stack = _planar_stack(flow, dev)
-    return stack if stack is not None else _radial_stack(flow, dev)
+    """The fused PlanarStack or RadialStack behind `flow` (the stacks without a
+    cnf_desc, whose parameters StackAdam steps as a tensor list), or None when
+    the flow is not an all-planar or all-radial Flow with fp32 parameters on
+    the ROCm device `dev`, the shape is outside the kernels' envelope, or the
+    family's switch (CNF_PLANAR_NATIVE=0 / CNF_RADIAL_NATIVE=0) is off."""
+    if torch.device(dev).type != "cuda":
+        return None
+    try:
+        from flows import flows as F
+        from cnf_hip import _lib
+        from cnf_hip.rowstack import stack_class
+    except ImportError:
+        return None
+    for family, native, layer, max_layers in (
+            ("planar", F.PLANAR_NATIVE, F.PlanarLayer, _lib.PLANAR_MAX_LAYERS),
+            ("radial", F.RADIAL_NATIVE, F.RadialLayer, _lib.RADIAL_MAX_LAYERS)):
+        if not native or not isinstance(flow, F.Flow):
+            continue
+        layers = list(flow.layers)
+        if not layers or not all(isinstance(l, layer) for l in layers):
+            continue
+        cls = stack_class(family)
+        ps = [p for l in layers for p in cls.layer_tensors(l)]
+        if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
+            continue
+        if not cls.compatible(layers, ps[0].device):
+            continue
+        if not (1 <= ps[0].numel() <= _lib.MAX_DIM and len(layers) <= max_layers):
+            continue
+        return flow._row_stack(cls, layers)
+    return None
 
 
 def _loader_order(n):

@@ -5,10 +5,11 @@
 // ending in cnf_metrics' record, cnf_score.h), all fp32.  The layer's log-det
 // is the reference's constant log(1) = 0: no kernel computes or stores one.
 //
-// Geometry, grid caps, tile staging and the record scheme are those of
-// cnf_planar.hip; the row helpers and the predict body are this file's own
-// copies (nothing is shared with cnf_planar.hip beyond the headers both
-// include, so the planar kernels' code is what it was).
+// Geometry, grid caps, workspace plan, argument checks, shape dispatch and the
+// lane helpers are cnf_rowflow.h's, shared with cnf_planar.hip.  The kernel
+// bodies -- tile staging, the predict body, the reverse-mode frame, the finish
+// kernel's record add -- are this file's own text, as the planar ones are
+// theirs: shared as helpers they compile to different code.
 //
 // Rows: one lane per row for D <= 16 (the row in registers), 16 lanes per row
 // for D <= 64, 64 lanes per row above (column c of a row sits in lane c % LPR,
@@ -43,82 +44,25 @@
 #include <cstdint>
 
 #include "cnf_internal.h"
+#include "cnf_rowflow.h"
 #include "cnf_score.h"
 #include "cnf_valu_io.h"
 
 namespace cnf {
 namespace {
 
+using namespace rowflow;
 using valu::wave_sum_dpp63;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxL = CNF_RADIAL_MAX_LAYERS;
-constexpr int kRegL = 10;        // r tape in registers / per-lane accumulators up to this depth
-constexpr int kFwdCap = 1024;    // grid caps in blocks
-constexpr int kBwdCap = 256;
-constexpr int kLdsWords = 3072;  // a wave's record in LDS up to this many floats (4 x 12 KB)
-constexpr int kFinThreads = 1024;
-constexpr int64_t kMaxRows = (int64_t)1 << 31;
 
 struct Ptrs {
   const float* p[3 * kMaxL];
 };
 
-struct Geo {
-  int lpr, cpl, dp, cs, ps, pw;
-  bool gacc;
-};
-
-Geo geometry(int D, int L) {
-  Geo g;
-  g.lpr = D <= 16 ? 1 : D <= 64 ? 16 : 64;
-  g.cpl = (D + g.lpr - 1) / g.lpr;
-  g.dp = g.lpr * g.cpl;
-  g.cs = g.dp + 8;
-  g.ps = D + 2;
-  g.pw = L * g.ps + 4;
-  g.gacc = g.pw > kLdsWords;
-  return g;
-}
-
-int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
-
-int fwd_blocks(const Geo& g, int64_t B) {
-  const int64_t rpb = kThreads / g.lpr;
-  const int64_t n = (B + rpb - 1) / rpb;
-  return (int)(n < 1 ? 1 : n > kFwdCap ? kFwdCap : n);
-}
-
-int bwd_blocks(const Geo& g, int64_t B) {
-  const int64_t rpb = kThreads / g.lpr;
-  int64_t cap = kBwdCap;
-  if (g.gacc) {
-    cap = ((int64_t)1 << 20) / g.pw;
-    cap = cap < 4 ? 4 : cap > kBwdCap ? kBwdCap : cap;
-  }
-  const int64_t n = (B + rpb - 1) / rpb;
-  return (int)(n < 1 ? 1 : n > cap ? cap : n);
-}
-
-int bwd_units(const Geo& g, int64_t B) { return bwd_blocks(g, B) * (g.gacc ? kWaves : 1); }
-
-struct Plan {
-  int64_t blob, sums, part, tape, total;  // float offsets / count
-};
-
-Plan plan(const Geo& g, int L, int64_t B) {
-  Plan p;
-  p.blob = 0;
-  p.sums = round64((int64_t)L * g.cs);
-  p.part = p.sums + round64(g.pw);
-  int64_t pf = (int64_t)bwd_units(g, B) * g.pw;
-  const int64_t lf = (int64_t)fwd_blocks(g, B) * 4;
-  if (lf > pf) pf = lf;
-  p.tape = p.part + round64(pf);
-  p.total = p.tape + (L > kRegL ? round64((int64_t)L * B) : 0);
-  return p;
-}
+// per layer: the constant record [z0 | 8 scalars], D + 2 row sums
+Geo radial_geometry(int D, int L) { return geometry(D, L, padded_dim(D) + 8, D + 2); }
+constexpr RowFamily kFamily{kMaxL, radial_geometry};
 
 // ---- per-layer constants --------------------------------------------------
 
@@ -145,28 +89,7 @@ __global__ __launch_bounds__(64) void k_radial_prep(Ptrs P, float* __restrict__ 
   }
 }
 
-// ---- lane helpers -----------------------------------------------------------
-
-// sum / max over the LPR lanes of a row (every lane gets the result)
-template <int LPR>
-__device__ __forceinline__ float row_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-template <int LPR>
-__device__ __forceinline__ float row_max(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-// sum over the wave's lanes that hold the same column slot (lane % LPR)
-template <int LPR>
-__device__ __forceinline__ float col_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= LPR; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+// ---- row steps --------------------------------------------------------------
 
 // One layer forward on the row's registers; returns r = ||x - z0||.  Padding
 // columns hold 0 in xv and in z0, so they add nothing to the norm and stay 0.
@@ -186,30 +109,6 @@ __device__ __forceinline__ float radial_step(float* xv, const float* __restrict_
 #pragma unroll
   for (int k = 0; k < CPL; ++k) xv[k] = fmaf(bh, d[k], xv[k]);
   return r;
-}
-
-// softmax of the row's final z: m, log-sum, and log p_y
-template <int LPR, int CPL>
-__device__ __forceinline__ void row_softmax(const float* xv, int gl, int D, int64_t yy, float& m,
-                                            float& lse, float& lpy) {
-  m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < CPL; ++k)
-    if (gl + LPR * k < D) m = fmaxf(m, xv[k]);
-  m = row_max<LPR>(m);
-  float se = 0.f, zy = 0.f;
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int c = gl + LPR * k;
-    if (c < D) {
-      se += expf(xv[k] - m);
-      if (c == yy) zy = xv[k];
-    }
-  }
-  se = row_sum<LPR>(se);
-  zy = row_sum<LPR>(zy);
-  lse = logf(se);
-  lpy = zy - (m + lse);
 }
 
 // the log-det is 0, so the loss is its cross-entropy term
@@ -709,15 +608,6 @@ __global__ __launch_bounds__(kFinThreads) void k_radial_finish(
 
 // ---- launches -------------------------------------------------------------------
 
-int hip_status(hipError_t err) {
-  if (err == hipSuccess) return CNF_OK;
-  set_hip_error(err);
-  return CNF_ERR_HIP;
-}
-
-bool mis4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
-bool mis8(const void* p) { return reinterpret_cast<uintptr_t>(p) & 7; }
-
 template <int LPR, int CPL>
 void launch_fwd(int blocks, hipStream_t s, const float* x, const float* blob, int D, int L, int cs,
                 int64_t B, float* z, float* z_all, const int64_t* y, int kind, float* part) {
@@ -753,66 +643,14 @@ void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
   }
 }
 
-#define CNF_RADIAL_DISPATCH(FN, ...)                     \
-  do {                                                   \
-    if (g.lpr == 1) {                                    \
-      switch (g.cpl) {                                   \
-        case 1: FN<1, 1>(__VA_ARGS__); break;            \
-        case 2: FN<1, 2>(__VA_ARGS__); break;            \
-        case 3: FN<1, 3>(__VA_ARGS__); break;            \
-        case 4: FN<1, 4>(__VA_ARGS__); break;            \
-        case 5: FN<1, 5>(__VA_ARGS__); break;            \
-        case 6: FN<1, 6>(__VA_ARGS__); break;            \
-        case 7: FN<1, 7>(__VA_ARGS__); break;            \
-        case 8: FN<1, 8>(__VA_ARGS__); break;            \
-        case 9: FN<1, 9>(__VA_ARGS__); break;            \
-        case 10: FN<1, 10>(__VA_ARGS__); break;          \
-        case 11: FN<1, 11>(__VA_ARGS__); break;          \
-        case 12: FN<1, 12>(__VA_ARGS__); break;          \
-        case 13: FN<1, 13>(__VA_ARGS__); break;          \
-        case 14: FN<1, 14>(__VA_ARGS__); break;          \
-        case 15: FN<1, 15>(__VA_ARGS__); break;          \
-        default: FN<1, 16>(__VA_ARGS__); break;          \
-      }                                                  \
-    } else if (g.lpr == 16) {                            \
-      switch (g.cpl) {                                   \
-        case 2: FN<16, 2>(__VA_ARGS__); break;           \
-        case 3: FN<16, 3>(__VA_ARGS__); break;           \
-        default: FN<16, 4>(__VA_ARGS__); break;          \
-      }                                                  \
-    } else {                                             \
-      switch (g.cpl) {                                   \
-        case 2: FN<64, 2>(__VA_ARGS__); break;           \
-        case 3: FN<64, 3>(__VA_ARGS__); break;           \
-        default: FN<64, 4>(__VA_ARGS__); break;          \
-      }                                                  \
-    }                                                    \
-  } while (0)
-
 int check_shape(int32_t dim, int32_t n_layers) {
-  if (dim < 1 || n_layers < 1) return CNF_ERR_DESC;
-  if (dim > CNF_MAX_DIM || n_layers > CNF_RADIAL_MAX_LAYERS) return CNF_ERR_UNSUPPORTED;
-  return CNF_OK;
+  return rowflow::check_shape(dim, n_layers, kMaxL);
 }
 
 // Common argument checks; fills the pointer table.
 int check_common(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
                  int64_t B, const void* ws, size_t ws_bytes, Ptrs* P, Geo* g, Plan* p) {
-  const int st = check_shape(dim, n_layers);
-  if (st != CNF_OK) return st;
-  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
-  if (!params) return CNF_ERR_NULL;
-  for (int i = 0; i < 3 * n_layers; ++i) {
-    if (!params[i]) return CNF_ERR_NULL;
-    if (mis4(params[i])) return CNF_ERR_ALIGN;
-    P->p[i] = params[i];
-  }
-  for (int i = 3 * n_layers; i < 3 * kMaxL; ++i) P->p[i] = nullptr;
-  *g = geometry(dim, n_layers);
-  *p = plan(*g, n_layers, B);
-  if (B > 0 && (!x || !ws || ws_bytes < (size_t)p->total * sizeof(float))) return CNF_ERR_NULL;
-  if (mis4(x) || mis4(ws)) return CNF_ERR_ALIGN;
-  return CNF_OK;
+  return rowflow::check_common(kFamily, dim, n_layers, params, x, B, ws, ws_bytes, P->p, g, p);
 }
 
 int run_prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, hipStream_t s) {
@@ -840,8 +678,8 @@ int run_forward(int32_t D, int32_t L, const float* const* params, const float* x
   if (st != CNF_OK) return st;
   const int blocks = fwd_blocks(g, B);
   float* part = loss ? w + p.part : nullptr;
-  CNF_RADIAL_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, z_all,
-                      loss ? y : nullptr, kind, part);
+  CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, z_all,
+                       loss ? y : nullptr, kind, part);
   st = hip_status(hipGetLastError());
   if (st != CNF_OK || !loss) return st;
   hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, part, blocks, 4, 0,
@@ -872,8 +710,8 @@ int run_predict(int32_t D, int32_t L, const float* const* params, const float* x
   if (st != CNF_OK) return st;
   score::Args sc;
   if (scoring) sc = score::make_args(y, bins, record);
-  CNF_RADIAL_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
-                      scoring ? &sc : nullptr);
+  CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
+                       scoring ? &sc : nullptr);
   return hip_status(hipGetLastError());
 }
 
@@ -929,7 +767,7 @@ int run_backward(int32_t D, int32_t L, const float* const* params, const float* 
   a.gacc = g.gacc ? 1 : 0;
   a.kind = kind;
   a.gscale = gscale;
-  CNF_RADIAL_DISPATCH(launch_bwd, blocks, lds, s, a);
+  CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, s, a);
   st = hip_status(hipGetLastError());
   if (st != CNF_OK) return st;
   hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, a.part, units, g.pw,
@@ -952,13 +790,7 @@ extern "C" int cnf_radial_param_count(int32_t dim, int32_t n_layers, int64_t* n_
 
 extern "C" int cnf_radial_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
                                           size_t* bytes) {
-  using namespace cnf;
-  if (!bytes) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers);
-  if (st != CNF_OK) return st;
-  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
-  *bytes = (size_t)plan(geometry(dim, n_layers), n_layers, B).total * sizeof(float);
-  return CNF_OK;
+  return cnf::rowflow::workspace_bytes(cnf::kFamily, dim, n_layers, B, bytes);
 }
 
 extern "C" int cnf_radial_forward(int32_t dim, int32_t n_layers, const float* const* params,

@@ -24,7 +24,8 @@ CNF_RADIAL_NATIVE=0 radial ones.  A radial stack's log-det is the reference's
 constant log(1) = 0: the native path returns the same 0-d fp32 zero.
 
 A planar or radial stack's other launches hang off the same kind of binding
-(cnf_hip/planar.py, cnf_hip/radial.py): the fused training step and loss
+(cnf_hip/planar.py, cnf_hip/radial.py over the base both share,
+cnf_hip/rowstack.py): the fused training step and loss
 evaluation, the calibrator's fused predict and score (cnf_planar_predict,
 cnf_radial_predict, ..._score) and the one-launch Adam step
 (cnf_adam_step_tensors); calibrators.TorchFlowCalibrator drives them, HIP-graph
@@ -93,25 +94,32 @@ def _native_eligible(layers, x):
     return True
 
 
-def _planar_eligible(layers, x):
-    """True when these layers can run as one fused planar stack on x."""
-    if not PLANAR_NATIVE or not (isinstance(x, torch.Tensor) and x.is_cuda):
-        return False
+def _row_class(layers, x):
+    """The stack class (PlanarStack / RadialStack) under which these layers can
+    run on x as one fused launch of a row-wise family, or None.  The family's
+    switch is read here, at call time, and with the input's device before
+    anything of cnf_hip is touched."""
+    family = getattr(layers[0], "_family", None) if layers else None
+    if family is None or not (PLANAR_NATIVE if family == "planar" else RADIAL_NATIVE):
+        return None
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        return None
     if x.dtype != torch.float32 or x.dim() != 2:
-        return False
-    if not layers or not all(isinstance(ly, PlanarLayer) for ly in layers):
-        return False
-    from cnf_hip.planar import PlanarStack
-    # PlanarLayer(params=...) tensors that sit on another device fall through
-    # to the torch ops, which fail there as the reference does
-    if not PlanarStack.compatible(layers, x.device):
-        return False
-    return x.shape[1] == layers[0].w.numel()
+        return None
+    from cnf_hip.rowstack import stack_class
+    cls = stack_class(family)
+    # every layer of the family's class; PlanarLayer(params=...) tensors that
+    # sit on another device fall through to the torch ops, which fail there as
+    # the reference does
+    if not cls.compatible(layers, x.device):
+        return None
+    return cls if x.shape[1] == cls.layer_tensors(layers[0])[0].numel() else None
 
 
-def _planar_run(stack, x, want_all):
-    """(zs list | final z, log-det) of a PlanarStack, or None when the shape is
-    outside the kernels' envelope."""
+def _row_run(stack, x, want_all):
+    """(zs list | final z, log-det) of a PlanarStack or RadialStack (whose
+    log-det is the 0-d zero), or None when the shape is outside the kernels'
+    envelope."""
     from cnf_hip._lib import UnsupportedShape
     try:
         if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
@@ -125,34 +133,16 @@ def _planar_run(stack, x, want_all):
         return None
 
 
-def _radial_eligible(layers, x):
-    """True when these layers can run as one fused radial stack on x."""
-    if not RADIAL_NATIVE or not (isinstance(x, torch.Tensor) and x.is_cuda):
-        return False
-    if x.dtype != torch.float32 or x.dim() != 2:
-        return False
-    if not layers or not all(isinstance(ly, RadialLayer) for ly in layers):
-        return False
-    from cnf_hip.radial import RadialStack
-    if not RadialStack.compatible(layers, x.device):
-        return False
-    return x.shape[1] == layers[0].z0.numel()
-
-
-def _radial_run(stack, x, want_all):
-    """(zs list | final z, the 0-d zero log-det) of a RadialStack, or None when
-    the shape is outside the kernels' envelope."""
-    from cnf_hip._lib import UnsupportedShape
-    try:
-        if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
-            out, ld = stack.forward_autograd(x, want_all=want_all)
-        else:
-            fin, ld, allt = stack.run(x, want_all=want_all)
-            out = allt if want_all else fin
-        return (list(out.unbind(0)) if want_all else out), ld
-    except UnsupportedShape as e:
-        _not_native(str(e))
+def _layer_native(layer, x):
+    """A PlanarLayer's or RadialLayer's forward as one fused launch on its own
+    single-layer stack (rebuilt when a parameter was replaced), or None."""
+    cls = _row_class([layer], x)
+    if cls is None:
         return None
+    st = getattr(layer, "_stack", None)
+    if st is None or any(t is not p for t, p in zip(st.param_tensors(), cls.layer_tensors(layer))):
+        st = layer._stack = cls([layer])
+    return _row_run(st, x, want_all=False)
 
 
 def _squeeze_ld(ld):
@@ -172,22 +162,22 @@ class Flow(nn.Module):
         # cnf_desc.options bits (cnf_hip._lib.OPT_*): keep launches off a kernel
         # family, for A/B runs and tests; 0 = the fastest kernel
         self.native_options = int(kwargs.get("native_options", 0))
-        self._stack = None
-        self._stack_key = None
-        self._pstack = None
-        self._pstack_key = None
-        self._rstack = None
-        self._rstack_key = None
+        self._drop_bindings(self.__dict__)
+
+    # the lazily built native bindings, each with the key it was built for:
+    # the CouplingStack, the PlanarStack, the RadialStack
+    _BINDINGS = ("_stack", "_pstack", "_rstack")
+
+    @classmethod
+    def _drop_bindings(cls, attrs):
+        for slot in cls._BINDINGS:
+            attrs[slot] = None
+            attrs[slot + "_key"] = None
 
     def __getstate__(self):
         # the native binding (ctypes descriptor, device blobs) is rebuilt lazily
         st = self.__dict__.copy()
-        st["_stack"] = None
-        st["_stack_key"] = None
-        st["_pstack"] = None
-        st["_pstack_key"] = None
-        st["_rstack"] = None
-        st["_rstack_key"] = None
+        self._drop_bindings(st)
         return st
 
     # -- native plumbing --------------------------------------------------
@@ -200,32 +190,33 @@ class Flow(nn.Module):
             self._stack_key = key
         return self._stack
 
+    def _row_stack(self, cls, layers):
+        """The stack of class `cls` over `layers` (list(self.layers)), kept in
+        the slot the class names (_pstack, _rstack) and rebuilt when a layer or
+        one of its parameters was replaced; a flow unpickled from before the
+        slot existed builds it as well."""
+        tensors = cls.layer_tensors
+        key = list(map(id, layers)) + [id(t) for ly in layers for t in tensors(ly)]
+        st = getattr(self, cls.slot, None)
+        if st is None or getattr(self, cls.slot + "_key") != key:
+            st = cls(layers)
+            setattr(self, cls.slot, st)
+            setattr(self, cls.slot + "_key", key)
+        return st
+
     def _planar_stack(self):
-        key = tuple((id(ly), id(ly.w), id(ly.u), id(ly.b)) for ly in self.layers)
-        if getattr(self, "_pstack", None) is None or self._pstack_key != key:
-            from cnf_hip.planar import PlanarStack
-            self._pstack = PlanarStack(list(self.layers))
-            self._pstack_key = key
-        return self._pstack
+        from cnf_hip.planar import PlanarStack
+        return self._row_stack(PlanarStack, list(self.layers))
 
     def _radial_stack(self):
-        key = tuple((id(ly), id(ly.z0), id(ly.a), id(ly.b)) for ly in self.layers)
-        if getattr(self, "_rstack", None) is None or self._rstack_key != key:
-            from cnf_hip.radial import RadialStack
-            self._rstack = RadialStack(list(self.layers))
-            self._rstack_key = key
-        return self._rstack
+        from cnf_hip.radial import RadialStack
+        return self._row_stack(RadialStack, list(self.layers))
 
     def invalidate_native(self):
         """Drop the native binding's prepared weights.  Needed only after writes
         that bypass torch's version counters (`p.data.copy_(...)`); optimizer
         steps, `load_state_dict` and in-place ops are tracked automatically."""
-        self._stack = None
-        self._stack_key = None
-        self._pstack = None
-        self._pstack_key = None
-        self._rstack = None
-        self._rstack_key = None
+        self._drop_bindings(self.__dict__)
         for ly in self.layers:
             if isinstance(ly, NvpCouplingLayer):
                 ly._stack = None
@@ -236,12 +227,9 @@ class Flow(nn.Module):
     def _try_native(self, x, inverse, want_all=True):
         """(zs list | final z, log-det) from one fused launch, or None."""
         layers = list(self.layers)
-        if not inverse and layers and isinstance(layers[0], PlanarLayer) \
-                and _planar_eligible(layers, x):
-            return _planar_run(self._planar_stack(), x, want_all)
-        if not inverse and layers and isinstance(layers[0], RadialLayer) \
-                and _radial_eligible(layers, x):
-            return _radial_run(self._radial_stack(), x, want_all)
+        cls = None if inverse else _row_class(layers, x)
+        if cls is not None:
+            return _row_run(self._row_stack(cls, layers), x, want_all)
         if not _native_eligible(layers, x):
             return None
         from cnf_hip._lib import UnsupportedShape
@@ -423,6 +411,7 @@ class PlanarLayer(nn.Module):
     """Planar flow (reference flows/flows.py:129-165); non-invertible.  On a
     ROCm device one fused launch (cnf_planar_forward, L = 1); torch ops on the
     host."""
+    _family = "planar"  # the row-wise family of cnf_hip.rowstack
 
     def __init__(self, dim=0, params=None):
         super().__init__()
@@ -444,18 +433,8 @@ class PlanarLayer(nn.Module):
         st["_stack"] = None
         return st
 
-    def _native(self, x):
-        if not _planar_eligible([self], x):
-            return None
-        st = getattr(self, "_stack", None)
-        if st is None or st.param_tensors()[0] is not self.w or st.param_tensors()[1] is not self.u \
-                or st.param_tensors()[2] is not self.b:
-            from cnf_hip.planar import PlanarStack
-            st = self._stack = PlanarStack([self])
-        return _planar_run(st, x, want_all=False)
-
     def forward(self, x):
-        out = self._native(x)
+        out = _layer_native(self, x)
         if out is not None:
             return out
         wtu = torch.dot(self.w, self.u)
@@ -472,6 +451,7 @@ class RadialLayer(nn.Module):
     """Radial flow (reference flows/flows.py:168-193); non-invertible.  Its
     log-det is the constant log(1) = 0, as in the reference.  On a ROCm device
     one fused launch (cnf_radial_forward, L = 1); torch ops on the host."""
+    _family = "radial"
 
     def __init__(self, dim):
         super().__init__()
@@ -486,18 +466,8 @@ class RadialLayer(nn.Module):
         st["_stack"] = None
         return st
 
-    def _native(self, x):
-        if not _radial_eligible([self], x):
-            return None
-        st = getattr(self, "_stack", None)
-        if st is None or st.param_tensors()[0] is not self.z0 \
-                or st.param_tensors()[1] is not self.a or st.param_tensors()[2] is not self.b:
-            from cnf_hip.radial import RadialStack
-            st = self._stack = RadialStack([self])
-        return _radial_run(st, x, want_all=False)
-
     def forward(self, x):
-        out = self._native(x)
+        out = _layer_native(self, x)
         if out is not None:
             return out
         b_hat = -self.a + torch.log1p(torch.exp(self.b))

@@ -146,7 +146,7 @@ def bench_fit_epoch(D, L, N):
                                 epochs=0, dev=dev)
     cal.flow.to(dev)
     xs, ys = cal.logits.to(dev), cal.target.to(dev)
-    stack = C._radial_stack(cal.flow, dev)
+    stack = C._tensor_stack(cal.flow, dev)
     run = C._EpochRunner(stack, StackAdam.like(stack, cal.optimizer), xs, ys, N)
     terms = torch.empty(a.reps, 3, dtype=torch.float32, device=dev)
     run.eager_epoch(terms[0])
