@@ -443,7 +443,7 @@ def _native_stack(flow, dev, need_vjp=True):
         return None
     try:
         from flows.flows import Flow, NvpCouplingLayer
-        from cnf_hip import _lib
+        import cnf_hip  # noqa: F401
     except ImportError:
         return None
     if not isinstance(flow, Flow) or not all(isinstance(l, NvpCouplingLayer) for l in flow.layers):
@@ -454,13 +454,9 @@ def _native_stack(flow, dev, need_vjp=True):
     if not need_vjp:
         return stack
     try:
-        import ctypes
-        n = ctypes.c_size_t()
-        st = _lib.lib().cnf_vjp_workspace_bytes(ctypes.byref(stack.desc), ctypes.c_int64(1),
-                                                ctypes.byref(n))
-    except Exception:
+        return stack if stack.has_native_vjp() else None
+    except Exception:  # no library to ask
         return None
-    return stack if st == 0 else None
 
 
 def _tensor_stack(flow, dev):
@@ -495,6 +491,13 @@ def _tensor_stack(flow, dev):
             continue
         return flow._row_stack(cls, layers)
     return None
+
+
+def _history(terms_all, epochs, N):
+    """The fit's history dict from the per-epoch (loss, ce, log-det) sums."""
+    hist = terms_all[:epochs] / N
+    return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
+            'log_det': list(hist[:, 2].unbind(0))}
 
 
 def _loader_order(n):
@@ -630,18 +633,18 @@ class TorchFlowCalibrator(Calibrator):
         logits = logits.to(self.dev)
         target = target.to(self.dev)
         self.flow.to(self.dev)
-        stack = _native_stack(self.flow, self.dev)
+        stack, fit = _native_stack(self.flow, self.dev), self._fit_native
+        if stack is None:
+            stack = _tensor_stack(self.flow, self.dev)
+            if stack is not None:
+                from cnf_hip import adam
+                if not adam.supports(self.optimizer):
+                    fit = self._fit_torch_step
         if stack is not None:
             # the captured epochs launch on the CURRENT device's stream: make
             # that the calibrator's `dev`, which need not be the current GPU
             with torch.cuda.device(logits.device):
-                history = self._fit_native(stack, logits, target, epochs, batch_size)
-        elif _tensor_stack(self.flow, self.dev) is not None:
-            from cnf_hip import adam
-            tstack = _tensor_stack(self.flow, self.dev)
-            fit = self._fit_native if adam.supports(self.optimizer) else self._fit_torch_step
-            with torch.cuda.device(logits.device):
-                history = fit(tstack, logits, target, epochs, batch_size)
+                history = fit(stack, logits, target, epochs, batch_size)
         else:
             history = self._fit_torch(logits, target, epochs, batch_size)
         self.flow.cpu()
@@ -721,9 +724,7 @@ class TorchFlowCalibrator(Calibrator):
         adam.store_into(self.optimizer)
         stack.invalidate()  # drop blobs / workspaces captured into a graph pool
         stack.release_workspace()
-        hist = terms_all[:epochs] / N
-        return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
-                'log_det': list(hist[:, 2].unbind(0))}
+        return _history(terms_all, epochs, N)
 
     def _fit_torch_step(self, stack, logits, target, epochs, batch_size):
         """The fit of a planar or radial stack under an optimizer the native
@@ -759,9 +760,7 @@ class TorchFlowCalibrator(Calibrator):
                                    terms_out=terms_all[e] if last else None)
         for p in params:
             p.grad = None
-        hist = terms_all[:epochs] / N
-        return {'loss': list(hist[:, 0].unbind(0)), 'ce': list(hist[:, 1].unbind(0)),
-                'log_det': list(hist[:, 2].unbind(0))}
+        return _history(terms_all, epochs, N)
 
     # -------------------------------------------------------------- predict
     def _device_flow(self):
@@ -777,30 +776,27 @@ class TorchFlowCalibrator(Calibrator):
         return self._replica[1]
 
     def _device_stack(self, logits):
-        """(stack, x, fused_score): the native stack of the resident replica,
-        the logits as an fp32 tensor on self.dev and whether the stack has a
-        one-launch score (a PlanarStack or RadialStack); (None, None, False)
-        when no native stack serves this flow there."""
+        """(stack, x): the native stack of the resident replica and the logits
+        as an fp32 tensor on self.dev; (None, None) when no native stack
+        serves this flow there."""
         if torch.device(self.dev).type != "cuda":
-            return None, None, False
+            return None, None
         flow = self._device_flow()
-        stack, fused_score = _native_stack(flow, self.dev, need_vjp=False), False
+        stack = _native_stack(flow, self.dev, need_vjp=False) or _tensor_stack(flow, self.dev)
         if stack is None:
-            stack, fused_score = _tensor_stack(flow, self.dev), True
-        if stack is None:
-            return None, None, False
+            return None, None
         if _on_device(logits):
             x = logits.detach().to(device=self.dev, dtype=torch.float)
         else:
             x = torch.as_tensor(np.asarray(logits), dtype=torch.float).to(self.dev)
         if self._lp_dev is None:
             self._lp_dev = torch.as_tensor(self.log_priors, dtype=torch.float, device=self.dev)
-        return stack, x, fused_score
+        return stack, x
 
     def _predict_device(self, logits):
         """predict()'s fp32 probabilities as a tensor on self.dev, or None when
         no native stack serves this flow there (then predict() runs on the host)."""
-        stack, x, _ = self._device_stack(logits)
+        stack, x = self._device_stack(logits)
         if stack is None:
             return None
         with torch.no_grad():
@@ -847,8 +843,8 @@ class TorchFlowCalibrator(Calibrator):
         coupling flow keeps
         its fused predict plus one cnf_metrics launch; without a native stack
         the host path scores predict()'s float64 probabilities."""
-        from cnf_hip.metrics import CalibrationSums, calibration_record
-        stack, x, fused_score = self._device_stack(logits)
+        from cnf_hip.metrics import CalibrationSums
+        stack, x = self._device_stack(logits)
         if stack is None:
             if _on_device(logits):
                 logits = logits.detach().cpu()
@@ -862,10 +858,7 @@ class TorchFlowCalibrator(Calibrator):
             return CalibrationSums(record, bins)
         y = _score_labels(target, x.device)
         with torch.no_grad():
-            if fused_score:
-                return CalibrationSums(stack.score(x, self._lp_dev, y, bins, record), bins)
-            return CalibrationSums(calibration_record(stack.predict(x, self._lp_dev), y, bins,
-                                                      record), bins)
+            return CalibrationSums(stack.score(x, self._lp_dev, y, bins, record), bins)
 
     def score(self, logits, target, bins=15):
         return self.score_sums(logits, target, bins).as_dict()

@@ -1,11 +1,10 @@
-"""On-device Adam over a stack's parameters in ONE launch (cnf_adam_step,
-include/cnf.h), fed by the flat gradient of cnf_loss_vjp /
-cnf_planar_loss_vjp.  Any stack that offers `param_tensors()` and
-`param_count()` works: a CouplingStack goes through the cnf_desc entry points
-(cnf_adam_step, _sched, _guarded), a stack without a `desc` (PlanarStack)
-through cnf_adam_step_tensors, the same kernel over an explicit tensor list.
-It is
-the optimizer half of the calibrator's fused training step (SURVEY 8(f) rank 1;
+"""On-device Adam over a stack's parameters in ONE launch
+(cnf_adam_step_tensors, include/cnf.h), fed by the flat gradient of the
+stack's loss_and_grads.  Every stack (cnf_hip.stack.Stack) goes through that
+one entry point, the kernel over an explicit tensor list built from
+`param_tensors()`; the cnf_desc entry points (cnf_adam_step, _sched, _guarded)
+derive the same list from a coupling descriptor and stay in the ABI for C
+callers.  It is the optimizer half of the calibrator's fused training step (SURVEY 8(f) rank 1;
 the reference steps torch.optim.Adam at its defaults, calibrators.py:239-295).
 Same update as torch.optim.Adam (amsgrad off), with torch's scalar rounding
 (the hyper-parameters cross the ABI as doubles).
@@ -20,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream, stats
+from .stack import _ptr, _stream, stats
 
 
 def supports(opt):
@@ -51,8 +50,7 @@ def group_hparams(torch_adam, stack):
 
 
 class StackAdam:
-    """Adam state (two flat moment buffers) for one stack (CouplingStack or
-    PlanarStack)."""
+    """Adam state (two flat moment buffers) for one stack."""
 
     def __init__(self, stack, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.stack = stack
@@ -60,6 +58,10 @@ class StackAdam:
                                                             float(eps), float(weight_decay))
         self.t = 0
         self._m = self._v = None
+        # the parameter tensors are fixed for a stack's life: their sizes, in
+        # flat-gradient order, are marshalled once
+        ps = stack.param_tensors()
+        self._numel = (ctypes.c_int64 * max(len(ps), 1))(*[p.numel() for p in ps])
 
     @classmethod
     def like(cls, stack, torch_adam):
@@ -103,15 +105,13 @@ class StackAdam:
         moments shaped like the parameter)."""
         if self._m is None:
             return
-        off = 0
-        for p in self.stack.param_tensors():
-            n = p.numel()
+        split = self.stack.split
+        for p, m, v in zip(self.stack.param_tensors(), split(self._m), split(self._v)):
             torch_adam.state[p] = {
                 "step": torch.tensor(float(self.t), dtype=torch.float32),
-                "exp_avg": self._m[off:off + n].view_as(p).clone(),
-                "exp_avg_sq": self._v[off:off + n].view_as(p).clone(),
+                "exp_avg": m.clone(),
+                "exp_avg_sq": v.clone(),
             }
-            off += n
 
     def sched_values(self, t):
         """torch.optim.Adam's two step-dependent scalars for step t, formed as
@@ -132,29 +132,30 @@ class StackAdam:
             self._m, self._v = self._m.to(dev), self._v.to(dev)
         return ps, dev
 
-    def _tensors_call(self, ps, dev, flat_grads, sched, skip):
-        """cnf_adam_step_tensors: the stack has no cnf_desc."""
-        n = len(ps)
-        arr = (ctypes.c_void_p * max(n, 1))(*[p.data_ptr() for p in ps])
-        numel = (ctypes.c_int64 * max(n, 1))(*[p.numel() for p in ps])
-        st = _lib.lib().cnf_adam_step_tensors(
-            ctypes.c_int32(n), numel, arr, _ptr(flat_grads), _ptr(self._m), _ptr(self._v),
-            ctypes.c_int64(self.t), ctypes.c_double(self.lr), _ptr(sched),
-            ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
-            ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _ptr(skip),
-            _stream(dev))
-        _lib.check("cnf_adam_step_tensors", st)
-
-    def _check_step(self, ps, dev, flat_grads):
+    def _step(self, flat_grads, sched, skip):
+        """One cnf_adam_step_tensors launch on the parameters' device; `sched`
+        and `skip` are device tensors or None."""
+        ps, dev = self._ensure_state()
         for p in ps:
             if not p.is_contiguous():
                 raise ValueError("StackAdam needs contiguous parameters")
-        if flat_grads.numel() != self.stack.param_count() or flat_grads.dtype != torch.float32 \
+        if flat_grads.numel() != self._m.numel() or flat_grads.dtype != torch.float32 \
                 or not flat_grads.is_contiguous() or flat_grads.device != dev:
             raise ValueError("StackAdam: the flat gradient must be contiguous fp32 [%d] on %s"
-                             % (self.stack.param_count(), dev))
-
-    def _done(self, ps):
+                             % (self._m.numel(), dev))
+        if skip is not None and (skip.dtype != torch.int32 or skip.device != dev):
+            raise ValueError("StackAdam.step: skip must be a device int32 flag on %s" % dev)
+        self.t += 1
+        n = len(ps)
+        arr = (ctypes.c_void_p * max(n, 1))(*[p.data_ptr() for p in ps])
+        with torch.cuda.device(dev):
+            st = _lib.lib().cnf_adam_step_tensors(
+                ctypes.c_int32(n), self._numel, arr, _ptr(flat_grads), _ptr(self._m),
+                _ptr(self._v), ctypes.c_int64(self.t), ctypes.c_double(self.lr), _ptr(sched),
+                ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
+                ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _ptr(skip),
+                _stream(dev))
+        _lib.check("cnf_adam_step_tensors", st)
         # the kernel wrote the parameters behind autograd's back: bump their
         # version counters, so every prepared-weight cache keyed on them (this
         # stack's and any other binding's) rebuilds
@@ -165,52 +166,10 @@ class StackAdam:
     def step_sched(self, flat_grads, sched):
         """One step whose scalars come from the device tensor `sched` [2]
         (graph capture: replays any step).  Advances the host step count."""
-        ps, dev = self._ensure_state()
-        self.t += 1
-        if not hasattr(self.stack, "desc"):
-            self._check_step(ps, dev, flat_grads)
-            with torch.cuda.device(dev):
-                self._tensors_call(ps, dev, flat_grads, sched, None)
-            return self._done(ps)
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        st = _lib.lib().cnf_adam_step_sched(
-            ctypes.byref(self.stack.desc), arr, _ptr(flat_grads), _ptr(self._m), _ptr(self._v),
-            _ptr(sched), ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
-            ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _stream(dev))
-        _lib.check("cnf_adam_step_sched", st)
-        self._done(ps)
+        self._step(flat_grads, sched, None)
 
     def step(self, flat_grads, skip=None):
         """One step.  skip: a device int32 flag (NonFiniteGuard.flag) read by
-        the kernel: non-zero leaves the parameters and moments untouched
-        (cnf_adam_step_guarded), with no host sync."""
-        ps, dev = self._ensure_state()
-        for p in ps:
-            if not p.is_contiguous():
-                raise ValueError("StackAdam needs contiguous parameters")
-        if skip is not None and (skip.dtype != torch.int32 or skip.device != dev):
-            raise ValueError("StackAdam.step: skip must be a device int32 flag on %s" % dev)
-        self.t += 1
-        if not hasattr(self.stack, "desc"):
-            self._check_step(ps, dev, flat_grads)
-            with torch.cuda.device(dev):
-                self._tensors_call(ps, dev, flat_grads, None, skip)
-            return self._done(ps)
-        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-        lib = _lib.lib()
-        if skip is not None:
-            st = lib.cnf_adam_step_guarded(
-                ctypes.byref(self.stack.desc), arr, _ptr(flat_grads), _ptr(self._m),
-                _ptr(self._v), ctypes.c_int64(self.t), ctypes.c_double(self.lr), None,
-                ctypes.c_double(self.betas[0]), ctypes.c_double(self.betas[1]),
-                ctypes.c_double(self.eps), ctypes.c_double(self.weight_decay), _ptr(skip),
-                _stream(dev))
-            _lib.check("cnf_adam_step_guarded", st)
-        else:
-            st = lib.cnf_adam_step(ctypes.byref(self.stack.desc), arr, _ptr(flat_grads),
-                                   _ptr(self._m), _ptr(self._v), ctypes.c_int64(self.t),
-                                   ctypes.c_double(self.lr), ctypes.c_double(self.betas[0]),
-                                   ctypes.c_double(self.betas[1]), ctypes.c_double(self.eps),
-                                   ctypes.c_double(self.weight_decay), _stream(dev))
-            _lib.check("cnf_adam_step", st)
-        self._done(ps)
+        the kernel: non-zero leaves the parameters and moments untouched, with
+        no host sync."""
+        self._step(flat_grads, None, skip)

@@ -20,14 +20,8 @@ import ctypes
 import torch
 
 from . import _lib
-
-# counts of native launches (tests assert the HIP path really ran); "torch_ops"
-# counts the launches that went through the torch.library operators
-stats = {"forward": 0, "inverse": 0, "prepare": 0, "vjp": 0, "loss_vjp": 0, "predict": 0,
-         "metrics": 0, "torch_ops": 0, "planar_forward": 0, "planar_vjp": 0,
-         "planar_loss_vjp": 0, "planar_predict": 0, "planar_score": 0,
-         "radial_forward": 0, "radial_vjp": 0, "radial_loss_vjp": 0, "radial_predict": 0,
-         "radial_score": 0}
+from .stack import Stack, StackFn, _ptr, _stream, _stream_key, stats, upstream_grads
+from .vjp import _torch_vjp
 
 # Dispatch through torch.ops.cnf (C++ operators, autograd in C++) when
 # libcnf_torch.so is built; False: the ctypes calls of the same C ABI.
@@ -38,22 +32,19 @@ def _ops():
     return _lib.torch_ops() if USE_TORCH_OPS else None
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _stream_key(device):
-    return (device, torch.cuda.current_stream(device).cuda_stream)
-
-
-class CouplingStack:
+class CouplingStack(Stack):
     """A fused stack of NvpCouplingLayers (flows/flows.py:68-126) sharing
     dim / hidden_size / scale / shift.  Layers keep owning their parameters;
     the stack only reads them (state_dict order) through cnf_prepare."""
+    family = "coupling"
+    _rows = "logits"
+    _fp32_why = " (the reference's nn.Linear weights are fp32)"
+    _stale = "weight or permutation"
+    # reverse-mode workspaces (per-block gradient partials) of every coupling
+    # stack: one per (entry point, device, stream).  Nothing is reserved for the
+    # calibrator's epoch runner: the workspaces a capture creates live in the
+    # graph's private pool.
+    _ws_cache = {}
 
     def __init__(self, layers, strict_nan=False, options=0):
         layers = list(layers)
@@ -131,10 +122,6 @@ class CouplingStack:
             self._vjp_ok = st == 0
         return self._vjp_ok
 
-    def param_tensors(self):
-        """ABI order (include/cnf.h cnf_param_tensor_count)."""
-        return self._params
-
     def _gather_params(self):
         out = []
         for ly in self.layers:
@@ -153,10 +140,7 @@ class CouplingStack:
 
     def state_key(self):
         """Identity of everything the prepared blob encodes."""
-        return (tuple([(p.data_ptr(), p._version) for p in self._params]), self._perm_state())
-
-    def requires_grad(self):
-        return any([p.requires_grad for p in self._params])
+        return (Stack.state_key(self), self._perm_state())
 
     def prepared(self, device):
         """Device blob for this stack, rebuilt only when a parameter or a
@@ -187,15 +171,14 @@ class CouplingStack:
         return blob
 
     # ---------------------------------------------------------------- launches
-    def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("native coupling path needs a ROCm device tensor")
-        if x.dtype != torch.float32:
-            raise TypeError("native coupling path is fp32 (the reference's nn.Linear weights "
-                            "are fp32); got %s" % x.dtype)
-        if x.dim() != 2 or x.shape[1] != self.dim:
-            raise ValueError("expected [B, %d] logits, got %s" % (self.dim, tuple(x.shape)))
-        return x.contiguous()
+    def _workspace(self, entry, cache, B, dev):
+        """(buffer, bytes) of <entry>_workspace_bytes for B rows: cache's
+        buffer for (entry, device, stream), grown on demand."""
+        fn = entry + "_workspace_bytes"
+        n = ctypes.c_size_t()
+        _lib.check(fn, getattr(_lib.lib(), fn)(ctypes.byref(self.desc), ctypes.c_int64(B),
+                                               ctypes.byref(n)))
+        return self._buffer(cache, (entry,) + _stream_key(dev), n.value, dev), n.value
 
     def run(self, x, inverse=False, want_all=False, want_final=True, blob=None):
         """Returns (final [B,D] or None, logdet [B], all [L,B,D] or None)."""
@@ -238,45 +221,89 @@ class CouplingStack:
         B = x.shape[0]
         dev = x.device
         blob = self.prepared(dev)
-        lib = _lib.lib()
-        n = ctypes.c_size_t()
-        _lib.check("cnf_forward_loss_workspace_bytes",
-                   lib.cnf_forward_loss_workspace_bytes(ctypes.byref(self.desc),
-                                                        ctypes.c_int64(B), ctypes.byref(n)))
-        # one workspace per (device, stream): launches on two streams never share
-        # the partial-sum records
-        sk = _stream_key(dev)
-        ws = self._loss_ws.get(sk)
-        if ws is None or ws.numel() < n.value:
-            ws = torch.zeros(max(n.value, 16), dtype=torch.uint8, device=dev)
-            self._loss_ws[sk] = ws
-        terms = torch.empty(3, dtype=torch.float32, device=dev) if terms_out is None else terms_out
-        if terms.numel() != 3 or terms.dtype != torch.float32 or terms.device != dev:
-            raise ValueError("forward_loss: terms_out must be fp32 [3] on %s" % dev)
+        # this stack's partial-sum records, one workspace per (device, stream)
+        ws, nws = self._workspace("cnf_forward_loss", self._loss_ws, B, dev)
+        terms = self._out_buffer(terms_out, 3, dev, "forward_loss: terms_out")
         z = torch.empty_like(x) if want_outputs else None
         ld = torch.empty(B, dtype=torch.float32, device=dev) if want_outputs else None
-        st = lib.cnf_forward_loss(ctypes.byref(self.desc), _ptr(blob), _ptr(x), _ptr(y),
-                                  ctypes.c_int32(kind), ctypes.c_float(det), _ptr(z), _ptr(ld),
-                                  _ptr(terms), ctypes.c_int64(B), _ptr(ws),
-                                  ctypes.c_size_t(n.value), _stream(dev))
+        st = _lib.lib().cnf_forward_loss(
+            ctypes.byref(self.desc), _ptr(blob), _ptr(x), _ptr(y), ctypes.c_int32(kind),
+            ctypes.c_float(det), _ptr(z), _ptr(ld), _ptr(terms), ctypes.c_int64(B), _ptr(ws),
+            ctypes.c_size_t(nws), _stream(dev))
         _lib.check("cnf_forward_loss", st)
         stats["forward"] += 1
         return terms, z, ld
 
-    def loss_and_grads(self, x, y, **kw):
-        """Fused forward + loss + reverse mode: vjp.loss_and_grads(self, ...)
-        as a method, the form the calibrator's epoch runner calls on either
-        kind of stack."""
-        from .vjp import loss_and_grads
-        return loss_and_grads(self, x, y, **kw)
+    def loss_and_grads(self, x, y, kind=_lib.LOSS_CAL, det=1.0, grad_scale=1.0, need_dx=False,
+                       grads_out=None, terms_out=None):
+        """Fused forward + loss + reverse mode (cnf_loss_vjp).  Returns
+        (terms[3], flat grads, dx) where terms = (sum of per-row loss, sum of
+        ce, sum of log-det) over THIS batch and grads = grad_scale * d(sum of
+        per-row loss)/d(params).  grads_out / terms_out: caller-provided
+        contiguous fp32 destinations (e.g. the two parts of one all-reduce
+        buffer)."""
+        x = x.contiguous()
+        y = y.contiguous().to(torch.int64)
+        B = x.shape[0]
+        dev = x.device
+        blob = self.prepared(dev)
+        ws, nws = self._workspace("cnf_vjp", self._ws_cache, B, dev)
+        what = "loss_and_grads: output buffer"
+        grads = self._out_buffer(grads_out, self.param_count(), dev, what)
+        terms = self._out_buffer(terms_out, 3, dev, what)
+        dx = torch.empty_like(x) if need_dx else None
+        st = _lib.lib().cnf_loss_vjp(
+            ctypes.byref(self.desc), _ptr(blob), _ptr(x), _ptr(y), ctypes.c_int32(kind),
+            ctypes.c_float(det), ctypes.c_float(grad_scale), _ptr(terms), _ptr(grads), _ptr(dx),
+            ctypes.c_int64(B), _ptr(ws), ctypes.c_size_t(nws), _stream(dev))
+        _lib.check("cnf_loss_vjp", st)
+        stats["loss_vjp"] += 1
+        return terms, grads, dx
 
-    def reserve_workspace(self, B, device):
-        """The epoch runner's hook; nothing to do here: this stack's workspaces
-        are per-stream caches, and the ones a capture creates live in the
-        graph's private pool."""
+    def _reverse(self, entry, x, g_out, g_ld, all_grads, need_dx, blob, ws):
+        """One cnf_vjp / cnf_vjp_inverse call: (status, dx or None, flat grads)."""
+        B, dev = x.shape[0], x.device
+        grads = torch.empty(self.param_count(), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(x) if need_dx else None
+        gz, gza, gld = upstream_grads(g_out, g_ld, all_grads, B)
+        st = getattr(_lib.lib(), entry)(
+            ctypes.byref(self.desc), _ptr(blob), _ptr(x), _ptr(gz), _ptr(gza), _ptr(gld),
+            _ptr(grads), _ptr(dx), ctypes.c_int64(B), _ptr(ws[0]), ctypes.c_size_t(ws[1]),
+            _stream(dev))
+        return st, dx, grads
 
-    def release_workspace(self):
-        pass
+    def vjp(self, x, g_out, g_ld, all_grads, need_dx, blob=None):
+        """(dx or None, [grad per parameter]) for the upstream gradients of
+        (z_all if all_grads else z_final, log-det); `blob`: the prepared weights
+        the forward ran with.  A shape without a native reverse mode goes to
+        torch autograd (vjp._torch_vjp)."""
+        x = x.contiguous()
+        try:
+            if blob is None:
+                blob = self.prepared(x.device)
+            ws = self._workspace("cnf_vjp", self._ws_cache, x.shape[0], x.device)
+        except _lib.UnsupportedShape:
+            return _torch_vjp(self, x, g_out, g_ld, all_grads, need_dx)
+        st, dx, grads = self._reverse("cnf_vjp", x, g_out, g_ld, all_grads, need_dx, blob, ws)
+        if st == -3:
+            return _torch_vjp(self, x, g_out, g_ld, all_grads, need_dx)
+        _lib.check("cnf_vjp", st)
+        stats["vjp"] += 1
+        return dx, self.split(grads)
+
+    def vjp_inverse(self, z, g_out, g_ld, all_grads, need_dx, blob=None):
+        """(dz or None, [grad per parameter]) of the INVERSE transform for the
+        upstream gradients of (x_all if all_grads else x_final, log-det)
+        (cnf_vjp_inverse, include/cnf.h)."""
+        z = z.contiguous()
+        if blob is None:
+            blob = self.prepared(z.device)
+        ws = self._workspace("cnf_vjp_inverse", self._ws_cache, z.shape[0], z.device)
+        st, dz, grads = self._reverse("cnf_vjp_inverse", z, g_out, g_ld, all_grads, need_dx,
+                                      blob, ws)
+        _lib.check("cnf_vjp_inverse", st)
+        stats["vjp"] += 1
+        return dz, self.split(grads)
 
     def predict(self, x, log_priors, want_logdet=False):
         """Calibrated probabilities softmax(log(softmax(flow(x - mean x)) + 1e-7)
@@ -288,9 +315,7 @@ class CouplingStack:
         x = self._check_input(x)
         B = x.shape[0]
         dev = x.device
-        lp = torch.as_tensor(log_priors, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        if lp.numel() != self.dim:
-            raise ValueError("log_priors must have %d entries" % self.dim)
+        lp = self._log_priors(log_priors, dev)
         blob = self.prepared(dev)
         probs = torch.empty_like(x)
         ld = torch.empty(B, dtype=torch.float32, device=dev) if want_logdet else None
@@ -306,6 +331,13 @@ class CouplingStack:
         p = torch.softmax(z, dim=1)
         probs = torch.softmax(torch.log(p + 1e-7) - lp, dim=1)
         return (probs, ld) if want_logdet else probs
+
+    def score(self, x, log_priors, y, bins=15, record=None):
+        """ADD the calibration record (cnf_hip.metrics) of predict(x,
+        log_priors) against the labels y into `record` and return it: the
+        fused predict plus one cnf_metrics launch."""
+        from .metrics import calibration_record
+        return calibration_record(self.predict(x, log_priors), y, bins, record)
 
     # -------------------------------------------------------------- autograd
     def forward_autograd(self, x, want_all):
@@ -323,7 +355,6 @@ class CouplingStack:
             stats["torch_ops"] += 1
             return ops.flow(x, blob, self.desc_ints, self._perms, want_all, ps)
         return _StackFn.apply(self, want_all, x, *ps)
-
 
     def has_native_vjp_inverse(self):
         """True when cnf_vjp_inverse serves this descriptor (strict_nan included)."""
@@ -350,7 +381,19 @@ class CouplingStack:
         return _InvStackFn.apply(self, want_all, z, *ps)
 
 
-class _InvStackFn(torch.autograd.Function):
+class _StackFn(StackFn):
+    """Flow.forward under autograd: cnf_forward forward, cnf_vjp backward on
+    the prepared blob the forward ran with."""
+
+    @staticmethod
+    def forward(ctx, stack, want_all, x, *params):
+        blob = stack.prepared(x.device)
+        fin, ld, allt = stack.run(x, inverse=False, want_all=want_all, blob=blob)
+        StackFn.saved(ctx, stack, want_all, x, blob=blob)
+        return (allt if want_all else fin), ld
+
+
+class _InvStackFn(StackFn):
     """Flow.backward (the inverse transform) under autograd: cnf_inverse
     forward, cnf_vjp_inverse backward."""
 
@@ -358,57 +401,5 @@ class _InvStackFn(torch.autograd.Function):
     def forward(ctx, stack, want_all, z, *params):
         blob = stack.prepared(z.device)
         fin, ld, allt = stack.run(z, inverse=True, want_all=want_all, blob=blob)
-        ctx.stack = stack
-        ctx.want_all = want_all
-        ctx.blob = blob
-        ctx.key = stack.state_key()
-        ctx.save_for_backward(z)
+        StackFn.saved(ctx, stack, want_all, z, vjp="vjp_inverse", blob=blob)
         return (allt if want_all else fin), ld
-
-    @staticmethod
-    def backward(ctx, g_out, g_ld):
-        from .vjp import stack_vjp_inverse
-        (z,) = ctx.saved_tensors
-        stack = ctx.stack
-        if stack.state_key() != ctx.key:
-            raise RuntimeError(
-                "one of the variables needed for gradient computation has been modified by an "
-                "inplace operation: a coupling-layer weight or permutation changed between the "
-                "native inverse and its backward")
-        dz, grads = stack_vjp_inverse(stack, z, g_out, g_ld, all_grads=ctx.want_all,
-                                      need_dz=ctx.needs_input_grad[2], blob=ctx.blob)
-        out = [None, None, dz]
-        for p, g in zip(stack.param_tensors(), grads):
-            out.append(g.view_as(p))
-        return tuple(out)
-
-
-class _StackFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, stack, want_all, x, *params):
-        blob = stack.prepared(x.device)
-        fin, ld, allt = stack.run(x, inverse=False, want_all=want_all, blob=blob)
-        ctx.stack = stack
-        ctx.want_all = want_all
-        ctx.blob = blob
-        ctx.key = stack.state_key()
-        ctx.save_for_backward(x)
-        return (allt if want_all else fin), ld
-
-    @staticmethod
-    def backward(ctx, g_out, g_ld):
-        from .vjp import stack_vjp
-        (x,) = ctx.saved_tensors
-        stack = ctx.stack
-        if stack.state_key() != ctx.key:
-            raise RuntimeError(
-                "one of the variables needed for gradient computation has been modified by an "
-                "inplace operation: a coupling-layer weight or permutation changed between the "
-                "native forward and its backward")
-        dx, grads = stack_vjp(stack, x, g_out, g_ld, all_grads=ctx.want_all,
-                              need_dx=ctx.needs_input_grad[2], blob=ctx.blob)
-        ps = stack.param_tensors()
-        out = [None, None, dx]
-        for p, g in zip(ps, grads):
-            out.append(g.view_as(p))
-        return tuple(out)

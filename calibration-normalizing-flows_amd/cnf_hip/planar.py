@@ -15,7 +15,8 @@ owning `w`, `u`, `b`; the library re-derives `u_hat` inside every call.
 
 Everything that does not depend on the family -- the parameter table, the
 checks, the workspace, the launch frame, `score`, the autograd backward -- is
-`cnf_hip.rowstack.RowStack`'s, shared with `RadialStack`; this module holds
+`cnf_hip.rowstack.RowStack`'s (over `cnf_hip.stack.Stack`, the base of every
+stack), shared with `RadialStack`; this module holds
 the launches whose arguments are planar's own (the log-det and its gradient).
 """
 import ctypes
@@ -24,7 +25,7 @@ import operator
 import torch
 
 from . import _lib, rowstack
-from .engine import _ptr
+from .stack import StackFn, _ptr, upstream_grads
 
 
 def workspace_bytes(dim, n_layers, B):
@@ -85,16 +86,7 @@ class PlanarStack(rowstack.RowStack):
         B, dev = x.shape[0], x.device
         grads = torch.empty(self.param_count(), dtype=torch.float32, device=dev)
         dx = torch.empty_like(x) if need_dx else None
-        gz = gza = None
-        if g_out is not None:
-            g_out = g_out.contiguous().float()
-            if all_grads:
-                gza = g_out
-            else:
-                gz = g_out
-        gld = g_ld.contiguous().float().reshape(-1) if g_ld is not None else None
-        if gld is not None and gld.numel() == 1 and B != 1:
-            gld = gld.expand(B).contiguous()
+        gz, gza, gld = upstream_grads(g_out, g_ld, all_grads, B)
         self._call("vjp", x, ws, _ptr(gz), _ptr(gza), _ptr(gld), _ptr(grads), _ptr(dx))
         return dx, grads
 
@@ -137,9 +129,9 @@ class PlanarStack(rowstack.RowStack):
         return _PlanarFn.apply(self, want_all, x, *self._params)
 
 
-class _PlanarFn(rowstack.RowFn):
+class _PlanarFn(StackFn):
     @staticmethod
     def forward(ctx, stack, want_all, x, *params):
         fin, ld, allt = stack.run(x, want_all=want_all)
-        rowstack.RowFn.saved(ctx, stack, want_all, x)
+        StackFn.saved(ctx, stack, want_all, x)
         return (allt if want_all else fin), ld

@@ -16,7 +16,8 @@ owning `z0`, `a`, `b`.
 
 Everything that does not depend on the family -- the parameter table, the
 checks, the workspace, the launch frame, `score`, the autograd backward -- is
-`cnf_hip.rowstack.RowStack`'s, shared with `PlanarStack`; this module holds
+`cnf_hip.rowstack.RowStack`'s (over `cnf_hip.stack.Stack`, the base of every
+stack), shared with `PlanarStack`; this module holds
 the launches whose arguments are radial's own (no log-det anywhere).
 """
 import ctypes
@@ -25,7 +26,7 @@ import operator
 import torch
 
 from . import _lib, rowstack
-from .engine import _ptr
+from .stack import StackFn, _ptr, upstream_grads
 
 
 def workspace_bytes(dim, n_layers, B):
@@ -82,13 +83,7 @@ class RadialStack(rowstack.RowStack):
         ws = self._ws(x)
         grads = torch.empty(self.param_count(), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x) if need_dx else None
-        gz = gza = None
-        if g_out is not None:
-            g_out = g_out.contiguous().float()
-            if all_grads:
-                gza = g_out
-            else:
-                gz = g_out
+        gz, gza, _ = upstream_grads(g_out, None, all_grads, x.shape[0])
         self._call("vjp", x, ws, _ptr(gz), _ptr(gza), _ptr(grads), _ptr(dx))
         return dx, grads
 
@@ -129,9 +124,9 @@ class RadialStack(rowstack.RowStack):
         return out, torch.log(torch.tensor(1.0))
 
 
-class _RadialFn(rowstack.RowFn):
+class _RadialFn(StackFn):
     @staticmethod
     def forward(ctx, stack, want_all, x, *params):
         fin, _, allt = stack.run(x, want_all=want_all)
-        rowstack.RowFn.saved(ctx, stack, want_all, x)
+        StackFn.saved(ctx, stack, want_all, x)
         return allt if want_all else fin

@@ -14,6 +14,8 @@ subclass declares
   sizes(D)              their element counts
 
 and keeps one workspace cache (`_ws_cache`, one buffer per (device, stream)).
+The parameter table, the checks, `split` and the autograd backward are the
+base's (cnf_hip/stack.py), shared with the coupling stack.
 The layers keep owning their parameters; the stack passes their device
 pointers on every call and the library re-derives the per-layer constants
 inside the call, so there is no prepared state to invalidate.  Buffers are
@@ -26,7 +28,7 @@ import functools
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream, _stream_key, stats
+from .stack import Stack, _ptr, _stream, _stream_key, stats
 
 
 @functools.lru_cache(maxsize=None)
@@ -53,7 +55,7 @@ def param_count(family, dim, n_layers):
     return n.value
 
 
-class RowStack:
+class RowStack(Stack):
     def __init_subclass__(cls):
         # entry -> (entry point, `stats` key): forward_loss counts as a forward
         cls._names = {e: ("cnf_%s_%s" % (cls.family, e),
@@ -96,43 +98,8 @@ class RowStack:
                     return False
         return True
 
-    def param_tensors(self):
-        """ABI order: the family's layer_tensors per layer (the state_dict order)."""
-        return self._params
-
     def param_count(self):
         return self.L * sum(self.sizes(self.dim))
-
-    def requires_grad(self):
-        return any(p.requires_grad for p in self._params)
-
-    def state_key(self):
-        return tuple((p.data_ptr(), p._version) for p in self._params)
-
-    def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("native %s path needs a ROCm device tensor" % self.family)
-        if x.dtype != torch.float32:
-            raise TypeError("native %s path is fp32; got %s" % (self.family, x.dtype))
-        if x.dim() != 2 or x.shape[1] != self.dim:
-            raise ValueError("expected [B, %d] rows, got %s" % (self.dim, tuple(x.shape)))
-        return x.contiguous()
-
-    def _log_priors(self, log_priors, dev):
-        lp = torch.as_tensor(log_priors, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        if lp.numel() != self.dim:
-            raise ValueError("log_priors must have %d entries" % self.dim)
-        return lp
-
-    @staticmethod
-    def _out_buffer(given, n, dev, what):
-        """`given`, checked, or a new fp32 [n] on dev when None."""
-        if given is None:
-            return torch.empty(n, dtype=torch.float32, device=dev)
-        if given.numel() != n or not given.is_contiguous() or given.dtype != torch.float32 \
-                or given.device != dev:
-            raise ValueError("%s must be contiguous fp32 [%d] on %s" % (what, n, dev))
-        return given
 
     def reserve_workspace(self, B, device):
         """Hold one private workspace for batches up to B rows on `device`,
@@ -154,11 +121,7 @@ class RowStack:
         n = workspace_bytes(self.family, self.dim, self.L, B)
         if self._own_ws is not None and B <= self._own_ws[1] and self._own_ws[0].device == dev:
             return self._own_ws[0], n
-        key = _stream_key(dev)
-        buf = self._ws_cache.get(key)
-        if buf is None or buf.numel() < n:
-            buf = self._ws_cache[key] = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
-        return buf, n
+        return self._buffer(self._ws_cache, _stream_key(dev), n, dev), n
 
     def _call(self, entry, x, ws, *args):
         """One launch of cnf_<family>_<entry> on x's device and torch's
@@ -188,44 +151,3 @@ class RowStack:
         ws = self._ws(x)
         self._call("score", x, ws, _ptr(lp), _ptr(y), ctypes.c_int32(bins), _ptr(record))
         return record
-
-    def invalidate(self):
-        """Nothing is prepared between calls (every call re-derives the layer
-        constants), so there is nothing to forget; kept so callers treat every
-        stack alike."""
-
-    def split(self, flat):
-        """Views of a flat gradient, one per parameter tensor."""
-        out, off = [], 0
-        for p in self._params:
-            out.append(flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        return out
-
-
-class RowFn(torch.autograd.Function):
-    """The autograd function of a family's forward: the subclass gives
-    forward(ctx, stack, want_all, x, *params), which calls saved(); backward is
-    the stack's vjp with the upstream gradients in forward's output order."""
-
-    @staticmethod
-    def saved(ctx, stack, want_all, x):
-        ctx.stack = stack
-        ctx.want_all = want_all
-        ctx.key = stack.state_key()
-        ctx.save_for_backward(x)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        (x,) = ctx.saved_tensors
-        stack = ctx.stack
-        if stack.state_key() != ctx.key:
-            raise RuntimeError(
-                "one of the variables needed for gradient computation has been modified by an "
-                "inplace operation: a %s-layer parameter changed between the native forward "
-                "and its backward" % stack.family)
-        dx, flat = stack.vjp(x, *grads, all_grads=ctx.want_all, need_dx=ctx.needs_input_grad[2])
-        out = [None, None, dx]
-        for i, g in enumerate(stack.split(flat)):
-            out.append(g if ctx.needs_input_grad[3 + i] else None)
-        return tuple(out)

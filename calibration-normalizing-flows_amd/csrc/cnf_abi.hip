@@ -1,8 +1,12 @@
 // extern "C" boundary of libcnf_hip.so (declared in include/cnf.h).
 // Validates the descriptor, picks the kernel family, and forwards to it.
-// No allocation, no host synchronisation, no global mutable state beyond the
-// thread-local last-HIP-error slot.
+// No allocation, no host synchronisation.  Global mutable state: the
+// thread-local last-HIP-error slot, and the mutex-guarded caches below of
+// what the device reports once (compute units, resident blocks per kernel).
 #include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <unordered_map>
 
 #include "cnf_internal.h"
 
@@ -11,6 +15,33 @@ namespace cnf {
 static thread_local int g_last_hip_error = 0;
 
 void set_hip_error(hipError_t e) { g_last_hip_error = (int)e; }
+
+// Both caches are filled from the device that is current at the first call and
+// assume every device of the process is the same part.
+int cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        v < 1)
+      v = 256;
+    return v;
+  }();
+  return n;
+}
+
+int resident_blocks(const void* fn, int threads, size_t lds) {
+  static std::mutex mu;
+  static std::unordered_map<const void*, int> cache;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(fn);
+  if (it != cache.end()) return it->second;
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) != hipSuccess || n < 1)
+    n = 1;
+  cache[fn] = n;
+  return n;
+}
 
 int derive_shape(const cnf_desc* d, Shape* s) {
   if (!d || !s) return CNF_ERR_NULL;
@@ -170,8 +201,7 @@ static int run(const cnf_desc* desc, const void* prepared, const float* in, floa
   if (B < 0) return CNF_ERR_BATCH;
   if (B == 0) return CNF_OK;
   if (!prepared || !in || (!out && !all)) return CNF_ERR_NULL;
-  auto mis = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3); };
-  if (mis(in) || mis(out) || mis(ld) || mis(all)) return CNF_ERR_ALIGN;
+  if (mis4(in) || mis4(out) || mis4(ld) || mis4(all)) return CNF_ERR_ALIGN;
   if (s.family == Family::kValu)
     return valu_run(s, prepared, in, out, ld, all, B, inverse, (hipStream_t)stream);
   return tile_run(s, prepared, in, out, ld, all, B, inverse, (hipStream_t)stream);
@@ -189,17 +219,22 @@ int cnf_inverse(const cnf_desc* desc, const void* prepared, const float* z, floa
   return run(desc, prepared, z, x, logdet, x_all, B, stream, true);
 }
 
+// cnf_forward_loss's workspace for a derived shape, B >= 0
+static int forward_loss_bytes(const Shape& s, int64_t B, size_t* bytes) {
+  if (s.family != Family::kValu) return CNF_ERR_UNSUPPORTED;
+  const int nb = B > 0 ? valu_loss_blocks(s, B) : 0;
+  // [16 B reserved][per-block partials: 4 floats each]
+  *bytes = (size_t)(1 + (nb > 0 ? nb : 1)) * 4 * sizeof(float);
+  return CNF_OK;
+}
+
 int cnf_forward_loss_workspace_bytes(const cnf_desc* desc, int64_t B, size_t* bytes) {
   Shape s;
   int st = derive_shape(desc, &s);
   if (st != CNF_OK) return st;
   if (!bytes) return CNF_ERR_NULL;
   if (B < 0) return CNF_ERR_BATCH;
-  if (s.family != Family::kValu) return CNF_ERR_UNSUPPORTED;
-  const int nb = B > 0 ? valu_loss_blocks(s, B) : 0;
-  // [16 B reserved][per-block partials: 4 floats each]
-  *bytes = (size_t)(1 + (nb > 0 ? nb : 1)) * 4 * sizeof(float);
-  return CNF_OK;
+  return forward_loss_bytes(s, B, bytes);
 }
 
 int cnf_forward_loss(const cnf_desc* desc, const void* prepared, const float* x,
@@ -215,29 +250,20 @@ int cnf_forward_loss(const cnf_desc* desc, const void* prepared, const float* x,
   if (s.family != Family::kValu) return CNF_ERR_UNSUPPORTED;
   if (!prepared || !loss_terms || (B > 0 && (!x || !y))) return CNF_ERR_NULL;
   size_t need = 0;
-  st = cnf_forward_loss_workspace_bytes(desc, B, &need);
+  st = forward_loss_bytes(s, B, &need);
   if (st != CNF_OK) return st;
   if (!workspace || workspace_bytes < need) return CNF_ERR_NULL;
-  auto mis = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3); };
-  if (mis(x) || mis(z) || mis(logdet)) return CNF_ERR_ALIGN;
+  if (mis4(x) || mis4(z) || mis4(logdet)) return CNF_ERR_ALIGN;
   float* ws = static_cast<float*>(workspace);
   if (B > 0) {
     st = valu_run(s, prepared, x, z, logdet, nullptr, B, false, (hipStream_t)stream, y, ws,
                   loss_kind, det, loss_terms);
     if (st != CNF_OK) return st;
   } else {
-    hipError_t e = hipMemsetAsync(loss_terms, 0, 3 * sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) {
-      set_hip_error(e);
-      return CNF_ERR_HIP;
-    }
+    st = hip_status(hipMemsetAsync(loss_terms, 0, 3 * sizeof(float), (hipStream_t)stream));
+    if (st != CNF_OK) return st;
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 int cnf_predict(const cnf_desc* desc, const void* prepared, const float* x,
@@ -252,8 +278,7 @@ int cnf_predict(const cnf_desc* desc, const void* prepared, const float* x,
   if (!narrow && !wide) return CNF_ERR_UNSUPPORTED;
   if (B == 0) return CNF_OK;
   if (!prepared || !x || !log_priors || !probs) return CNF_ERR_NULL;
-  auto mis = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3); };
-  if (mis(x) || mis(probs) || mis(logdet) || mis(log_priors)) return CNF_ERR_ALIGN;
+  if (mis4(x) || mis4(probs) || mis4(logdet) || mis4(log_priors)) return CNF_ERR_ALIGN;
   if (wide)  // k_wide16's predict mode (centre + flow + softmax + prior correction)
     return wide_run(s, prepared, x, probs, logdet, B, false, (hipStream_t)stream, log_priors);
   return sgpr_run(s, prepared, x, probs, logdet, nullptr, B, false, (hipStream_t)stream, nullptr,

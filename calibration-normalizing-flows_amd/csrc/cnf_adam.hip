@@ -120,12 +120,7 @@ int adam_tensors(int nt, const int64_t* numel, float* const* params, const float
     if (gx == 0) continue;  // every tensor of the chunk is empty
     hipLaunchKernelGGL(k_adam, dim3(gx, (unsigned)n_here), dim3(256), 0, (hipStream_t)stream, a);
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 // A coupling stack's tensor sizes in ABI order: per layer, per net, per

@@ -65,10 +65,5 @@ extern "C" int cnf_guard_nonfinite(const float* data, int64_t n, int32_t* flag, 
   const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(2048, (n + per_block - 1) / per_block));
   hipLaunchKernelGGL(k_guard, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, data, n,
                      vec, flag);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }

@@ -92,6 +92,44 @@ inline int64_t idx_bytes(const Shape& s) {
 int derive_shape(const cnf_desc* d, Shape* s);
 void set_hip_error(hipError_t e);
 
+// ---- host helpers of every translation unit (internal linkage or hidden:
+// none of them joins the library's exported symbols) ----
+
+// cnf_status of a HIP call; a failure is kept for cnf_last_hip_error
+static inline int hip_status(hipError_t err) {
+  if (err == hipSuccess) return CNF_OK;
+  set_hip_error(err);
+  return CNF_ERR_HIP;
+}
+// ... of the launches an entry point has issued: the tail of every *_run
+static inline int launch_status() { return hip_status(hipGetLastError()); }
+
+// a non-null pointer off its 4- / 8-byte alignment
+static inline bool mis4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
+static inline bool mis8(const void* p) { return reinterpret_cast<uintptr_t>(p) & 7; }
+
+// The prepared blob's parts: the forward / inverse gather tables, the layer
+// flags and the start of the weights region (a family adds its region offset).
+struct BlobView {
+  const int32_t *fq, *iq, *flags;
+  const float* W;
+};
+static inline BlobView blob_view(const Shape& s, const void* prepared) {
+  const char* base = static_cast<const char*>(prepared);
+  BlobView v;
+  v.fq = reinterpret_cast<const int32_t*>(base);
+  v.iq = v.fq + s.L * s.D;
+  v.flags = v.iq + s.L * s.D;
+  v.W = reinterpret_cast<const float*>(base + idx_bytes(s));
+  return v;
+}
+
+// Compute units of the current device (256 when the query fails), and the
+// blocks of kernel `fn` one of them keeps resident at this block size and
+// dynamic LDS (at least 1); both cached (cnf_abi.hip).
+__attribute__((visibility("hidden"))) int cu_count();
+__attribute__((visibility("hidden"))) int resident_blocks(const void* fn, int threads, size_t lds);
+
 // ---- kernel-family entry points (return cnf_status) ----
 int valu_supported(const Shape& s);  // -> valu_id or -1
 int valu_run(const Shape& s, const void* prepared, const float* in, float* out, float* ld,

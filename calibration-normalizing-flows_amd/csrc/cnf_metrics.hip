@@ -211,10 +211,5 @@ extern "C" int cnf_metrics(const float* probs, const int64_t* y, int32_t dim, in
   else
     hipLaunchKernelGGL(k_metrics<64>, dim3(blocks), dim3(kThreads), 0, s, probs, y, dim, bins, B,
                        e, record);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }

@@ -166,20 +166,11 @@ void launch_predict(hipStream_t s, const float* x, const double* tx, const doubl
     hipLaunchKernelGGL((k_predict<64, 4, LDS>), g, t, 0, s, x, tx, ty, nt, cap, lp, probs, D, B);
 }
 
-int hip_status(hipError_t err) {
-  if (err == hipSuccess) return CNF_OK;
-  set_hip_error(err);
-  return CNF_ERR_HIP;
-}
-
 int check_shape(int32_t dim) {
   if (dim < 2) return CNF_ERR_DESC;
   if (dim > CNF_MAX_DIM) return CNF_ERR_UNSUPPORTED;
   return CNF_OK;
 }
-
-bool mis4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
-bool mis8(const void* p) { return reinterpret_cast<uintptr_t>(p) & 7; }
 
 }  // namespace
 }  // namespace cnf
@@ -202,5 +193,5 @@ extern "C" int cnf_pav_predict(const float* x, int32_t dim, int64_t B, const dou
     launch_predict<true>(s, x, thr_x, thr_y, n_thr, cap, log_priors, probs, dim, B);
   else
     launch_predict<false>(s, x, thr_x, thr_y, n_thr, cap, log_priors, probs, dim, B);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }

@@ -655,7 +655,7 @@ int check_common(int32_t dim, int32_t n_layers, const float* const* params, cons
 
 int run_prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, hipStream_t s) {
   hipLaunchKernelGGL(k_radial_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }
 
 int run_forward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
@@ -680,11 +680,11 @@ int run_forward(int32_t D, int32_t L, const float* const* params, const float* x
   float* part = loss ? w + p.part : nullptr;
   CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, z_all,
                        loss ? y : nullptr, kind, part);
-  st = hip_status(hipGetLastError());
+  st = launch_status();
   if (st != CNF_OK || !loss) return st;
   hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, part, blocks, 4, 0,
                      w + p.sums, terms, (float*)nullptr, w + p.blob, D, L, g.dp, g.cs);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }
 
 // predict (sc == null) or score
@@ -712,7 +712,7 @@ int run_predict(int32_t D, int32_t L, const float* const* params, const float* x
   if (scoring) sc = score::make_args(y, bins, record);
   CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
                        scoring ? &sc : nullptr);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }
 
 int run_backward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
@@ -768,12 +768,12 @@ int run_backward(int32_t D, int32_t L, const float* const* params, const float* 
   a.kind = kind;
   a.gscale = gscale;
   CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, s, a);
-  st = hip_status(hipGetLastError());
+  st = launch_status();
   if (st != CNF_OK) return st;
   hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, a.part, units, g.pw,
                      L * g.ps, w + p.sums, loss ? terms : (float*)nullptr, grads, w + p.blob, D, L,
                      g.dp, g.cs);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }
 
 }  // namespace

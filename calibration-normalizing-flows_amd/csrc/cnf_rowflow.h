@@ -146,14 +146,7 @@ __device__ __forceinline__ void row_softmax(const float* xv, int gl, int D, int6
 
 // ---- host side ------------------------------------------------------------------
 
-inline int hip_status(hipError_t err) {
-  if (err == hipSuccess) return CNF_OK;
-  set_hip_error(err);
-  return CNF_ERR_HIP;
-}
-
-inline bool mis4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
-inline bool mis8(const void* p) { return reinterpret_cast<uintptr_t>(p) & 7; }
+// hip_status, launch_status, mis4 and mis8 are cnf_internal.h's (the enclosing namespace)
 
 // FN<LPR, CPL>(args...) for the geometry `g` in scope
 #define CNF_ROWFLOW_DISPATCH(FN, ...)                    \

@@ -441,15 +441,6 @@ void launch(int32_t kind, int blocks, hipStream_t s, const float* x, const int64
     launch_full<MODE>(blocks, s, x, y, a, b, lp, part, probs, D, B);
 }
 
-int hip_status(hipError_t err) {
-  if (err == hipSuccess) return CNF_OK;
-  set_hip_error(err);
-  return CNF_ERR_HIP;
-}
-
-bool mis4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
-bool mis8(const void* p) { return reinterpret_cast<uintptr_t>(p) & 7; }
-
 }  // namespace
 }  // namespace cnf
 
@@ -497,11 +488,11 @@ extern "C" int cnf_scaling_loss_grad(const float* x, const int64_t* y, int32_t k
     launch<kGrad>(kind, blocks, s, x, y, a, b, nullptr, part, nullptr, dim, B);
   else
     launch<kLoss>(kind, blocks, s, x, y, a, b, nullptr, part, nullptr, dim, B);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return hip_status(err);
+  const int st2 = launch_status();
+  if (st2 != CNF_OK) return st2;
   hipLaunchKernelGGL(k_scale_finish, dim3((unsigned)((words + kWaves - 1) / kWaves)),
                      dim3(kThreads), 0, s, part, blocks, (int)words, sums);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }
 
 extern "C" int cnf_scaling_predict(const float* x, int32_t kind, int32_t dim, const double* a,
@@ -518,5 +509,5 @@ extern "C" int cnf_scaling_predict(const float* x, int32_t kind, int32_t dim, co
   if (B == 0) return CNF_OK;
   launch<kPredict>(kind, grid_blocks(kind, dim, B), (hipStream_t)stream, x, nullptr, a, b,
                    log_priors, nullptr, probs, dim, B);
-  return hip_status(hipGetLastError());
+  return launch_status();
 }

@@ -49,9 +49,7 @@
 // the hot loop has no data-dependent branches and no scratch.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
 #include "cnf_internal.h"
 #include "cnf_valu_common.h"
@@ -762,16 +760,9 @@ size_t lds_bytes(const Shape& s, const KV& k) {
   return (size_t)kWaves * k.tr * s.D * 4;
 }
 
-int resident_blocks(const KV& k, size_t lds) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, int> cache;
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find((const void*)k.fn);
-  if (it != cache.end()) return it->second;
-  int n = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.fn, kWaves * 64, lds) != hipSuccess ||
-      n < 1)
-    n = 1;
+// resident blocks of k over the whole device
+int grid_cap(const KV& k, size_t lds) {
+  int n = resident_blocks((const void*)k.fn, kWaves * 64, lds);
   // at most kGridWps blocks per CU even where the occupancy query
   // allows more: at 7 per CU (forward, 71 VGPRs) the last ~10 % of a 2^20-row
   // grid was not resident at launch and started ~18 us late (tools/sgpr_trace.py).
@@ -780,12 +771,7 @@ int resident_blocks(const KV& k, size_t lds) {
   // A/B passes); 7 spills the loss build
   constexpr int kGridWps = 6;
   if (n > kGridWps * 4 / kWaves) n = kGridWps * 4 / kWaves;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus < 1)
-    cus = 256;
-  cache[(const void*)k.fn] = n * cus;
-  return n * cus;
+  return n * cu_count();
 }
 
 const KV* pick(const SEntry* e, const Shape& s, int mode, bool all) {
@@ -802,7 +788,7 @@ const KV* pick(const SEntry* e, const Shape& s, int mode, bool all) {
 int64_t grid_for(const KV& k, const Shape& s, int64_t B) {
   const int64_t ntiles = (B + k.tr - 1) / k.tr;
   const int64_t want = (ntiles + kWaves - 1) / kWaves;
-  int64_t cap = resident_blocks(k, lds_bytes(s, k));
+  int64_t cap = grid_cap(k, lds_bytes(s, k));
   // A short batch whose tiles fall evenly on the SIMDs but not on their
   // resident waves ends in a tail at low occupancy (2^20 rows: 8 tiles per
   // SIMD on 6 waves run as 6, then 2 on 2 waves).  There, the largest count
@@ -811,14 +797,7 @@ int64_t grid_for(const KV& k, const Shape& s, int64_t B) {
   // a small share, and more waves hide more latency).  2^20 rows: 29.36 vs
   // 30.31 us per loss call, 24.54 vs 25.05 us forward; 2^21 -0.5 / -1.5 %
   // (profiles/r06_ab_even_grid.jsonl).
-  static const int cus = []() {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        c < 1)
-      c = 256;
-    return c;
-  }();
+  const int cus = cu_count();
   const int64_t simds = (int64_t)cus * 4, wmax = cap / cus;
   if (ntiles % simds == 0) {
     const int64_t T = ntiles / simds;
@@ -865,11 +844,7 @@ int sgpr_run(const Shape& s, const void* prepared, const float* in, float* out, 
   const int mode = log_priors ? kPredict : (loss_ws ? kLoss : (inverse ? kInv : kFwd));
   const KV* k = pick(e, s, mode, all != nullptr);
   if (!k) return CNF_ERR_UNSUPPORTED;
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
-  const int32_t* inv_q = fwd_q + s.L * s.D;
-  const int32_t* flags = inv_q + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.sp_region;
+  const BlobView v = blob_view(s, prepared);
   KArgs a{};
   a.out = out;
   a.ld = ld;
@@ -881,16 +856,11 @@ int sgpr_run(const Shape& s, const void* prepared, const float* in, float* out, 
   a.det = det;
   const int64_t nblk = grid_for(*k, s, B);
   hipLaunchKernelGGL(k->fn, dim3((unsigned)nblk), dim3(kWaves * 64), lds_bytes(s, *k), st, in, B,
-                     W, inverse ? inv_q : fwd_q, flags, log_priors, a);
+                     v.W + s.sp_region, inverse ? v.iq : v.fq, v.flags, log_priors, a);
   // the block-order sum of the loss records: a one-block follow-up launch
   // (in-launch sums measured slower: cnf_valu_io.h reduce_rows4_block)
   if (mode == kLoss) reduce_partials(loss_ws + 4, (int)nblk, 4, 0, nullptr, loss_terms, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 }  // namespace cnf

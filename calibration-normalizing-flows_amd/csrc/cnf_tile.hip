@@ -372,22 +372,14 @@ int tile_run(const Shape& s, const void* prepared, const float* in, float* out, 
   if (!all && s.wide_floats > 0 && wide_ok(s))
     return wide_run(s, prepared, in, out, ld, B, inverse, st);
   TileArgs a = make_args(s);
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
-  const int32_t* inv_q = fwd_q + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s));
+  const BlobView v = blob_view(s, prepared);
   const int64_t vecs_per_block = (int64_t)s.tile_waves * kTileRows;
   dim3 grid((unsigned)((B + vecs_per_block - 1) / vecs_per_block)), block(64 * s.tile_waves);
   auto fn = inverse ? (s.strict ? k_tile<true, true> : k_tile<true, false>)
                     : (s.strict ? k_tile<false, true> : k_tile<false, false>);
-  hipLaunchKernelGGL(fn, grid, block, s.tile_lds_bytes, st, a, W, inverse ? inv_q : fwd_q, in, out,
+  hipLaunchKernelGGL(fn, grid, block, s.tile_lds_bytes, st, a, v.W, inverse ? v.iq : v.fq, in, out,
                      ld, all, B);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 int prepare_run(const Shape& s, const float* const* params, void* prepared, hipStream_t st) {
@@ -521,11 +513,8 @@ int prepare_run(const Shape& s, const float* const* params, void* prepared, hipS
   }
   flush_jobs();
   flush_idx();
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
+  const int status = launch_status();
+  if (status != CNF_OK) return status;
   if (tiled && s.wide_floats > 0) return wide_prepare(s, params, prepared, st);
   return CNF_OK;
 }

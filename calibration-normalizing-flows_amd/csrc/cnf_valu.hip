@@ -23,9 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
 #include "cnf_internal.h"
 #include "cnf_valu_common.h"
@@ -281,30 +279,6 @@ const Entry& entry_of(const Shape& s) {
   return s.valu_id >= kLBase ? kLTable[s.valu_id - kLBase] : kTable[s.valu_id];
 }
 
-int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
-
-int resident_blocks(KFn fn, int threads) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, int> cache;
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find((const void*)fn);
-  if (it != cache.end()) return it->second;
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, 0) != hipSuccess || n < 1)
-    n = 1;
-  cache[(const void*)fn] = n;
-  return n;
-}
-
 }  // namespace
 
 int valu_supported(const Shape& s) {
@@ -332,7 +306,7 @@ static int64_t blocks_for(const Shape& s, const Variant* var, KFn fn, int64_t B)
   const int64_t tr = (int64_t)var->rows * var->rw;
   int64_t nblk = (B + tr - 1) / tr;
   if (var->persist) {
-    const int64_t cap = (int64_t)cu_count() * resident_blocks(fn, var->rows);
+    const int64_t cap = (int64_t)cu_count() * resident_blocks((const void*)fn, var->rows, 0);
     if (nblk > cap) nblk = cap;
   }
   return nblk;
@@ -366,11 +340,7 @@ int valu_run(const Shape& s, const void* prepared, const float* in, float* out, 
   const Entry& e = entry_of(s);
   if (e.nf != s.valu_net_floats) return CNF_ERR_DESC;  // host/device layout disagree
   const Variant* var = pick_variant(s, B);
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
-  const int32_t* inv_q = fwd_q + s.L * s.D;
-  const int32_t* flags = inv_q + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s));
+  const BlobView v = blob_view(s, prepared);
   auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   int vec = al(in) && al(out) && al(all);
   KFn fn = var->fn[inverse ? 1 : 0][s.strict ? 1 : 0];
@@ -380,17 +350,12 @@ int valu_run(const Shape& s, const void* prepared, const float* in, float* out, 
   if (lds < (size_t)3 * var->rows * 4 + 4 * 65) lds = (size_t)3 * var->rows * 4 + 4 * 65;
   if (var->wl) lds += (size_t)s.L * s.nets * s.valu_net_floats * 4 * var->wl;
   if (lds > 160 * 1024) return CNF_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(var->rows), lds, st, W,
-                     inverse ? inv_q : fwd_q, flags, in, out, ld, all, B, s.L, s.scale, s.shift,
+  hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(var->rows), lds, st, v.W,
+                     inverse ? v.iq : v.fq, v.flags, in, out, ld, all, B, s.L, s.scale, s.shift,
                      s.any_perm ? 1 : 0, vec, y, loss_ws ? loss_ws + 4 : nullptr, kind, det,
                      s.alt_mask ? 1 : 0);
   if (loss_ws) reduce_partials(loss_ws + 4, (int)nblk, 4, 0, nullptr, loss_terms, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 }  // namespace cnf

@@ -27,8 +27,6 @@
 #include <cstdint>
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
-#include <unordered_map>
 #include <type_traits>
 
 #include "cnf_internal.h"
@@ -591,29 +589,30 @@ size_t lds_v2(const Shape& s) { return (size_t)(kV2TR * s.D + 32 * kV2SS) * 4; }
 
 // persistent grid: as many one-wave blocks as fit, at most one per tile
 int64_t grid_v2(const Shape& s, VFn2 fn, int64_t B) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, int> cache;
-  int cap;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find((const void*)fn);
-    if (it != cache.end()) {
-      cap = it->second;
-    } else {
-      int n = 0, dev = 0, cus = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64, lds_v2(s)) != hipSuccess ||
-          n < 1)
-        n = 1;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus < 1)
-        cus = 256;
-      cap = n * cus;
-      cache[(const void*)fn] = cap;
-    }
-  }
+  const int64_t cap = (int64_t)resident_blocks((const void*)fn, 64, lds_v2(s)) * cu_count();
   const int64_t nt = (B + kV2TR - 1) / kV2TR;
   return nt < cap ? nt : cap;
+}
+
+// both variants' grids (loss / generic, same grid rule): the workspace is laid
+// out for the larger
+int64_t grid_v2_max(const Shape& s, const V2Entry* e2, int64_t B) {
+  return std::max(grid_v2(s, pick_v2(e2, s, true), B), grid_v2(s, pick_v2(e2, s, false), B));
+}
+
+// The reverse-mode path of a shape: k_vjp2 (packed-pair SGPR), k_vjp
+// (row-resident VALU), the layer-at-a-time MFMA sweeps (the tile family, and
+// narrow shapes outside both row-resident kernels: L > 8, wide hidden layers),
+// or none.
+enum class VjpPath { kV2, kRows, kLayerwise, kNone };
+
+VjpPath vjp_path(const Shape& s) {
+  if (s.family != Family::kTile) {
+    if (find_v2(s)) return VjpPath::kV2;
+    const VEntry* e = find_entry(s);
+    if (e && lds_bytes(s, *e) <= 64 * 1024) return VjpPath::kRows;
+  }
+  return wvjp_ok(s) ? VjpPath::kLayerwise : VjpPath::kNone;
 }
 
 }  // namespace
@@ -659,21 +658,16 @@ size_t v2_stash_offset(const Shape& s, int64_t nblk) {
 }
 
 int vjp_workspace(const Shape& s, int64_t B, size_t* bytes) {
-  if (s.family == Family::kTile) return wvjp_workspace(s, B, bytes);
-  if (!find_v2(s)) {  // narrow shapes outside both row-resident kernels
-    const VEntry* e = find_entry(s);
-    if (!e || lds_bytes(s, *e) > 64 * 1024) return wvjp_workspace(s, B, bytes);
+  switch (vjp_path(s)) {
+    case VjpPath::kNone: return CNF_ERR_UNSUPPORTED;
+    case VjpPath::kLayerwise: return wvjp_workspace(s, B, bytes);
+    case VjpPath::kV2:
+      // the stash: L x DT x (B rounded up to even) floats (k_vjp2's pair stores)
+      *bytes = v2_stash_offset(s, grid_v2_max(s, find_v2(s), B)) +
+               (size_t)s.L * (((B > 0 ? B : 1) + 1) & ~(int64_t)1) * s.DT * 4;
+      return CNF_OK;
+    case VjpPath::kRows: break;
   }
-  if (const V2Entry* e2 = find_v2(s)) {
-    // the larger of the two variants (loss / generic) -- same grid rule
-    const int64_t g = std::max(grid_v2(s, pick_v2(e2, s, true), B),
-                               grid_v2(s, pick_v2(e2, s, false), B));
-    // the stash: L x DT x (B rounded up to even) floats (k_vjp2's pair stores)
-    *bytes = v2_stash_offset(s, g) + (size_t)s.L * (((B > 0 ? B : 1) + 1) & ~(int64_t)1) * s.DT * 4;
-    return CNF_OK;
-  }
-  const VEntry* e = find_entry(s);
-  if (!e || lds_bytes(s, *e) > 64 * 1024) return CNF_ERR_UNSUPPORTED;
   *bytes = (size_t)(grid_for(B) > 0 ? grid_for(B) : 1) * partial_stride(s) * 4;
   return CNF_OK;
 }
@@ -682,24 +676,22 @@ int vjp_run(const Shape& s, const void* prepared, const float* x, const int64_t*
             const float* gz, const float* gz_all, const float* gld, int kind, float det,
             float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B, void* ws,
             size_t ws_bytes, hipStream_t st) {
-  bool layerwise = s.family == Family::kTile;
-  if (!layerwise && !find_v2(s)) {
-    const VEntry* e = find_entry(s);
-    layerwise = !e || lds_bytes(s, *e) > 64 * 1024;
-  }
-  if (layerwise)
+  const VjpPath path = vjp_path(s);
+  if (path == VjpPath::kNone) return CNF_ERR_UNSUPPORTED;
+  if (path == VjpPath::kLayerwise)
     return wvjp_run(s, prepared, x, y, gz, gz_all, gld, kind, det, grad_scale, loss_terms, grads,
                     dx, B, ws, ws_bytes, st);
-  if (const V2Entry* e2 = find_v2(s)) {
-    size_t need = 0;
-    int r = vjp_workspace(s, B, &need);
-    if (r != CNF_OK) return r;
-    if (!ws || ws_bytes < need) return CNF_ERR_NULL;
-    const char* base = static_cast<const char*>(prepared);
-    const int32_t* fq = reinterpret_cast<const int32_t*>(base);
-    const int32_t* iq = fq + s.L * s.D;
-    const int32_t* flags = iq + s.L * s.D;
-    const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.vp_region;
+  size_t need = 0;
+  int r = vjp_workspace(s, B, &need);
+  if (r != CNF_OK) return r;
+  if (!ws || ws_bytes < need) return CNF_ERR_NULL;
+  const BlobView v = blob_view(s, prepared);
+  const bool loss = kind >= 0;
+  const int P = (int)(s.layer_floats * s.L);
+  const int PS = partial_stride(s);
+  float* partials = static_cast<float*>(ws);
+  if (path == VjpPath::kV2) {
+    const V2Entry* e2 = find_v2(s);
     VArgs2 a{};
     a.x = x;
     a.y = y;
@@ -707,60 +699,32 @@ int vjp_run(const Shape& s, const void* prepared, const float* x, const int64_t*
     a.gz_all = gz_all;
     a.gld = gld;
     a.dx = dx;
-    a.partials = static_cast<float*>(ws);
-    const int64_t nblk = B > 0 ? grid_v2(s, pick_v2(e2, s, kind >= 0), B) : 0;
-    const int64_t gmax = std::max(grid_v2(s, pick_v2(e2, s, true), B),
-                                  grid_v2(s, pick_v2(e2, s, false), B));
-    a.stash = reinterpret_cast<float*>(static_cast<char*>(ws) + v2_stash_offset(s, gmax));
+    a.partials = partials;
+    VFn2 fn = pick_v2(e2, s, loss);
+    const int64_t nblk = B > 0 ? grid_v2(s, fn, B) : 0;
+    a.stash = reinterpret_cast<float*>(static_cast<char*>(ws) +
+                                       v2_stash_offset(s, grid_v2_max(s, e2, B)));
     a.B = B;
     a.L = s.L;
     a.kind = kind;
     a.det = det;
     a.grad_scale = grad_scale;
-    a.P = (int)(s.layer_floats * s.L);
-    a.PS = partial_stride(s);
-    const bool loss = kind >= 0;
-    VFn2 fn = pick_v2(e2, s, loss);
+    a.P = P;
+    a.PS = PS;
     if (nblk > 0)
-      hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(64), lds_v2(s), st, W, fq, iq, flags, a);
-    reduce_partials(a.partials, (int)nblk, a.PS, a.P, grads, loss_terms, st);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-      set_hip_error(err);
-      return CNF_ERR_HIP;
-    }
-    return CNF_OK;
+      hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(64), lds_v2(s), st, v.W + s.vp_region, v.fq,
+                         v.iq, v.flags, a);
+    reduce_partials(partials, (int)nblk, PS, P, grads, loss_terms, st);
+    return launch_status();
   }
   const VEntry* e = find_entry(s);
-  if (!e) return CNF_ERR_UNSUPPORTED;
-  const size_t lds = lds_bytes(s, *e);
-  if (lds > 64 * 1024) return CNF_ERR_UNSUPPORTED;
-  size_t need = 0;
-  int r = vjp_workspace(s, B, &need);
-  if (r != CNF_OK) return r;
-  if (!ws || ws_bytes < need) return CNF_ERR_NULL;
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fq = reinterpret_cast<const int32_t*>(base);
-  const int32_t* iq = fq + s.L * s.D;
-  const int32_t* flags = iq + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s));
-  const int P = (int)(s.layer_floats * s.L);
-  const int PS = partial_stride(s);
-  float* partials = static_cast<float*>(ws);
   const int64_t nblk = grid_for(B);
-  if (nblk > 0) {
-    const bool loss = kind >= 0;
-    hipLaunchKernelGGL(e->fn[loss ? 1 : 0], dim3((unsigned)nblk), dim3(kVRows), lds, st, W, fq,
-                       iq, flags, x, y, gz, gz_all, gld, dx, partials, B, s.L, s.scale, s.shift,
-                       s.any_perm ? 1 : 0, kind, det, grad_scale, P, PS);
-  }
+  if (nblk > 0)
+    hipLaunchKernelGGL(e->fn[loss ? 1 : 0], dim3((unsigned)nblk), dim3(kVRows), lds_bytes(s, *e),
+                       st, v.W, v.fq, v.iq, v.flags, x, y, gz, gz_all, gld, dx, partials, B, s.L,
+                       s.scale, s.shift, s.any_perm ? 1 : 0, kind, det, grad_scale, P, PS);
   reduce_partials(partials, (int)nblk, PS, P, grads, loss_terms, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 }  // namespace cnf

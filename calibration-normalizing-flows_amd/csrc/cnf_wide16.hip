@@ -1368,11 +1368,8 @@ int wide_prepare(const Shape& s, const float* const* params, void* prepared, hip
         g.bdst = -1;
       }
     hipLaunchKernelGGL(k_prepare_wide16, dim3(a.nseg, 8), dim3(256), 0, st, a, region);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-      set_hip_error(err);
-      return CNF_ERR_HIP;
-    }
+    const int status = launch_status();
+    if (status != CNF_OK) return status;
   }
   return CNF_OK;
 }
@@ -1382,22 +1379,15 @@ int wide_run(const Shape& s, const void* prepared, const float* in, float* out, 
   const WEntry16* e = w16find(s);
   if (!e) return CNF_ERR_UNSUPPORTED;
   if (log_priors && inverse) return CNF_ERR_UNSUPPORTED;
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
-  const int32_t* inv_q = fwd_q + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.wide_region;
+  const BlobView v = blob_view(s, prepared);
   const int64_t rows_per_block = (int64_t)kRows * kWaves;
   const dim3 grid((unsigned)((B + rows_per_block - 1) / rows_per_block)), block(64 * kWaves);
   WFn fn = e->fn[s.nets - 1][log_priors ? 2 : (inverse ? 1 : 0)];
   const size_t lds = (size_t)(state_floats(s.D) + 2 * kAC * 64) * 4;  // state areas, two A stages
-  hipLaunchKernelGGL(fn, grid, block, lds, st, W, inverse ? inv_q : fwd_q, in, out, ld, B,
+  hipLaunchKernelGGL(fn, grid, block, lds, st, v.W + s.wide_region, inverse ? v.iq : v.fq, in, out,
+                     ld, B,
                      s.L, log_priors);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 int wide16_train_layout(const Shape& s, WTrain16Layout* out) {
@@ -1412,9 +1402,7 @@ int wide16_train_forward(const Shape& s, const void* prepared, const float* x, f
                          const WSeed16* seed, hipStream_t st) {
   const WEntry16* e = w16find(s);
   if (!e || s.nets < 1 || s.nets > 2) return CNF_ERR_UNSUPPORTED;
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* fwd_q = reinterpret_cast<const int32_t*>(base);
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.wide_region;
+  const BlobView v = blob_view(s, prepared);
   const int64_t rows_per_block = (int64_t)kRows * kWaves;
   const dim3 grid((unsigned)((B + rows_per_block - 1) / rows_per_block)), block(64 * kWaves);
   SeedArgs sa{};
@@ -1428,14 +1416,10 @@ int wide16_train_forward(const Shape& s, const void* prepared, const float* x, f
     sa.grad_scale = seed->grad_scale;
     sa.kind = seed->kind;
   }
-  hipLaunchKernelGGL(e->tfwd[s.nets - 1], grid, block, w16_lds(s), st, W, fwd_q, x, zst, ld, tape,
+  hipLaunchKernelGGL(e->tfwd[s.nets - 1], grid, block, w16_lds(s), st, v.W + s.wide_region, v.fq, x,
+                     zst, ld, tape,
                      tbits, B, s.L, Cp, Dp, sa);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 int wide16_train_backward(const Shape& s, const void* prepared, const float* gz,
@@ -1443,20 +1427,14 @@ int wide16_train_backward(const Shape& s, const void* prepared, const float* gz,
                           const uint32_t* tbits, float* gbuf, int64_t B, hipStream_t st) {
   const WEntry16* e = w16find(s);
   if (!e || s.nets < 1 || s.nets > 2) return CNF_ERR_UNSUPPORTED;
-  const char* base = static_cast<const char*>(prepared);
-  const int32_t* inv_q = reinterpret_cast<const int32_t*>(base) + s.L * s.D;
-  const float* W = reinterpret_cast<const float*>(base + idx_bytes(s)) + s.wide_region;
+  const BlobView v = blob_view(s, prepared);
   const int64_t LF = w16_la(e, s.nets) + (int64_t)s.nets * e->nb;
   const int64_t rows_per_block = (int64_t)kRows * kWaves;
   const dim3 grid((unsigned)((B + rows_per_block - 1) / rows_per_block)), block(64 * kWaves);
-  hipLaunchKernelGGL(e->tbwd[s.nets - 1], grid, block, w16_lds(s), st, W + s.L * LF, inv_q, gz,
+  hipLaunchKernelGGL(e->tbwd[s.nets - 1], grid, block, w16_lds(s), st,
+                     v.W + s.wide_region + s.L * LF, v.iq, gz,
                      gz_all, dx, gld, tape, tbits, gbuf, B, s.L);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
+  return launch_status();
 }
 
 }  // namespace cnf

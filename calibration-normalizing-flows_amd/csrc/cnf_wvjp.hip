@@ -1205,15 +1205,6 @@ int64_t lin_off(const Shape& s, int k) {
   return o;
 }
 
-int check_launch() {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_hip_error(err);
-    return CNF_ERR_HIP;
-  }
-  return CNF_OK;
-}
-
 int gemm_nc(int cols) { return std::min(kBN / 32, (cols + 31) / 32); }
 
 size_t gemm_lds(int cols, int K, bool pair) {
@@ -1350,7 +1341,7 @@ int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const
   const int64_t PL = s.layer_floats, PS = al64(PL);
   float* part = W + p.part;
   if (PL > 0 && hipMemsetAsync(part, 0, (size_t)p.nkb * PS * 4, st) != hipSuccess)
-    return check_launch();
+    return launch_status();
   int r = wide16_train_backward(s, prepared, g[0], gz_all, dx, gld, tape, tbits, W + p.gbuf, B, st);
   if (r != CNF_OK) return r;
   const int64_t Bp = wide16_blocks(B) * 32;
@@ -1405,7 +1396,7 @@ int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const
     }
     reduce_partials(part, (int)p.nkb, (int)PS, (int)PL, grads + (int64_t)l * PL, nullptr, st);
   }
-  return check_launch();
+  return launch_status();
 }
 
 }  // namespace
@@ -1447,8 +1438,7 @@ struct Runner {
   Runner(const Shape& s_, const Plan& p_, void* ws, const void* prepared, int64_t B_,
          hipStream_t st_)
       : s(s_), p(p_), W(static_cast<float*>(ws)),
-        plain(reinterpret_cast<const float*>(static_cast<const char*>(prepared) + idx_bytes(s_)) +
-              s_.plain_region),
+        plain(blob_view(s_, prepared).W + s_.plain_region),
         geom(geo(s_)), B(B_), st(st_), D(s_.D), DT(s_.DT), DC(s_.DC), NL(s_.n_lin), L(s_.L),
         PL(s_.layer_floats), PS(al64(s_.layer_floats)), Dp(geo(s_).Dp),
         wave_blocks((unsigned)std::min<int64_t>((B_ + 3) / 4, 16384)) {}
@@ -1550,7 +1540,7 @@ struct Runner {
     // the legacy alternate mask odd and even layers mask different positions
     if (s.alt_mask && dw_calls > 0 &&
         hipMemsetAsync(part, 0, (size_t)p.nkb * PS * 4, st) != hipSuccess)
-      return check_launch();
+      return launch_status();
     ++dw_calls;
     DwArgs da{};
     da.partials = part;
@@ -1597,9 +1587,9 @@ struct Runner {
 
 int empty_batch(const Shape& s, float* grads, float* loss_terms, hipStream_t st) {
   const int64_t P = s.layer_floats * s.L;
-  if (P > 0 && hipMemsetAsync(grads, 0, (size_t)P * 4, st) != hipSuccess) return check_launch();
-  if (loss_terms && hipMemsetAsync(loss_terms, 0, 3 * 4, st) != hipSuccess) return check_launch();
-  return check_launch();
+  if (P > 0 && hipMemsetAsync(grads, 0, (size_t)P * 4, st) != hipSuccess) return launch_status();
+  if (loss_terms && hipMemsetAsync(loss_terms, 0, 3 * 4, st) != hipSuccess) return launch_status();
+  return launch_status();
 }
 
 }  // namespace
@@ -1623,7 +1613,7 @@ int wvjp_run(const Shape& s, const void* prepared, const float* x, const int64_t
   if (!ws || ws_bytes < (size_t)p.total * 4) return CNF_ERR_NULL;
   if (B == 0) return empty_batch(s, grads, loss_terms, st);
   Runner R(s, p, ws, prepared, B, st);
-  const int32_t* fq = reinterpret_cast<const int32_t*>(prepared);
+  const int32_t* fq = blob_view(s, prepared).fq;
   const int D = s.D, NL = s.n_lin, L = s.L;
   float* W = R.W;
   float* ld = W + p.ld;
@@ -1646,7 +1636,7 @@ int wvjp_run(const Shape& s, const void* prepared, const float* x, const int64_t
                      g[0], gld, W + p.seed, B, R.geom);
   if (kind >= 0) reduce_partials(W + p.seed, (int)p.nseed, 4, 0, nullptr, loss_terms, st);
   if (R.PL > 0 && hipMemsetAsync(W + p.part, 0, (size_t)p.nkb * R.PS * 4, st) != hipSuccess)
-    return check_launch();
+    return launch_status();
 
   // ---- backward sweep ----
   for (int l = L - 1; l >= 0; --l) {
@@ -1667,7 +1657,7 @@ int wvjp_run(const Shape& s, const void* prepared, const float* x, const int64_t
     }
     cur ^= 1;
   }
-  return check_launch();
+  return launch_status();
 }
 
 // Reverse mode of the INVERSE transform (flows/flows.py:114-126, Flow.backward
@@ -1689,7 +1679,7 @@ int wvjp_inv_run(const Shape& s, const void* prepared, const float* z, const flo
   if (!ws || ws_bytes < (size_t)p.total * 4) return CNF_ERR_NULL;
   if (B == 0) return empty_batch(s, grads, nullptr, st);
   Runner R(s, p, ws, prepared, B, st);
-  const int32_t* iq = reinterpret_cast<const int32_t*>(prepared) + s.L * s.D;
+  const int32_t* iq = blob_view(s, prepared).iq;
   const int D = s.D, NL = s.n_lin, L = s.L;
   float* W = R.W;
   float* gld = W + p.gld;
@@ -1711,7 +1701,7 @@ int wvjp_inv_run(const Shape& s, const void* prepared, const float* z, const flo
                      -1, 0.f, 1.f, gx, gx_all ? gx_all + (int64_t)(L - 1) * B * D : nullptr,
                      gld_in, g[1], gld, W + p.seed, B, R.geom);
   if (R.PL > 0 && hipMemsetAsync(W + p.part, 0, (size_t)p.nkb * R.PS * 4, st) != hipSuccess)
-    return check_launch();
+    return launch_status();
 
   // ---- backward sweep over the steps, last first ----
   for (int i = L - 1; i >= 0; --i) {
@@ -1731,7 +1721,7 @@ int wvjp_inv_run(const Shape& s, const void* prepared, const float* z, const flo
                        gx_all && i > 0 ? gx_all + (int64_t)(i - 1) * B * D : nullptr,
                        iq + l * D, B, D, i == 0 && dz == nullptr);
   }
-  return check_launch();
+  return launch_status();
 }
 
 }  // namespace cnf

@@ -67,17 +67,21 @@ def _not_native(reason):
         warnings.warn("cnf: running torch ops on the GPU (%s)" % reason, RuntimeWarning)
 
 
-def _needs_grad(x, module):
-    if not torch.is_grad_enabled():
-        return False
-    return x.requires_grad or any(p.requires_grad for p in module.parameters())
+def _device_rows(x):
+    """True when x is a 2-d fp32 tensor on a ROCm device."""
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 \
+        and x.dim() == 2
+
+
+def _strict(obj):
+    """The strictness rule of a Flow or a layer: its own `strict_nan` when
+    set, else CNF_STRICT_NAN."""
+    return STRICT_NAN if obj.strict_nan is None else bool(obj.strict_nan)
 
 
 def _native_eligible(layers, x):
     """True when these layers can run as one fused native stack on x."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda):
-        return False
-    if x.dtype != torch.float32 or x.dim() != 2:
+    if not _device_rows(x):
         return False
     if not layers or not all(isinstance(ly, NvpCouplingLayer) for ly in layers):
         return False
@@ -102,9 +106,7 @@ def _row_class(layers, x):
     family = getattr(layers[0], "_family", None) if layers else None
     if family is None or not (PLANAR_NATIVE if family == "planar" else RADIAL_NATIVE):
         return None
-    if not (isinstance(x, torch.Tensor) and x.is_cuda):
-        return None
-    if x.dtype != torch.float32 or x.dim() != 2:
+    if not _device_rows(x):
         return None
     from cnf_hip.rowstack import stack_class
     cls = stack_class(family)
@@ -116,16 +118,23 @@ def _row_class(layers, x):
     return cls if x.shape[1] == cls.layer_tensors(layers[0])[0].numel() else None
 
 
-def _row_run(stack, x, want_all):
-    """(zs list | final z, log-det) of a PlanarStack or RadialStack (whose
-    log-det is the 0-d zero), or None when the shape is outside the kernels'
-    envelope."""
+def _run_stack(stack, x, want_all, inverse=False):
+    """(zs list | final z, log-det) from one fused launch of any stack (a
+    RadialStack's log-det is the 0-d zero), under autograd when a gradient is
+    wanted, or None when the shape is outside the kernels' envelope.  Only a
+    CouplingStack has an inverse."""
     from cnf_hip._lib import UnsupportedShape
     try:
         if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
-            out, ld = stack.forward_autograd(x, want_all=want_all)
+            if inverse:  # cnf_vjp_inverse (strict_nan included)
+                out, ld = stack.inverse_autograd(x, want_all=want_all)
+            else:
+                out, ld = stack.forward_autograd(x, want_all=want_all)
         else:
-            fin, ld, allt = stack.run(x, want_all=want_all)
+            if inverse:
+                fin, ld, allt = stack.run(x, inverse=True, want_all=want_all)
+            else:
+                fin, ld, allt = stack.run(x, want_all=want_all)
             out = allt if want_all else fin
         return (list(out.unbind(0)) if want_all else out), _squeeze_ld(ld)
     except UnsupportedShape as e:
@@ -142,7 +151,7 @@ def _layer_native(layer, x):
     st = getattr(layer, "_stack", None)
     if st is None or any(t is not p for t, p in zip(st.param_tensors(), cls.layer_tensors(layer))):
         st = layer._stack = cls([layer])
-    return _row_run(st, x, want_all=False)
+    return _run_stack(st, x, want_all=False)
 
 
 def _squeeze_ld(ld):
@@ -222,31 +231,17 @@ class Flow(nn.Module):
                 ly._stack = None
 
     def _strict(self):
-        return STRICT_NAN if self.strict_nan is None else bool(self.strict_nan)
+        return _strict(self)
 
     def _try_native(self, x, inverse, want_all=True):
         """(zs list | final z, log-det) from one fused launch, or None."""
         layers = list(self.layers)
         cls = None if inverse else _row_class(layers, x)
         if cls is not None:
-            return _row_run(self._row_stack(cls, layers), x, want_all)
+            return _run_stack(self._row_stack(cls, layers), x, want_all)
         if not _native_eligible(layers, x):
             return None
-        from cnf_hip._lib import UnsupportedShape
-        stack = self._native_stack()
-        try:
-            if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
-                if inverse:  # cnf_vjp_inverse (strict_nan included)
-                    out, ld = stack.inverse_autograd(x, want_all=want_all)
-                else:
-                    out, ld = stack.forward_autograd(x, want_all=want_all)
-            else:
-                fin, ld, allt = stack.run(x, inverse=inverse, want_all=want_all)
-                out = allt if want_all else fin
-            return (list(out.unbind(0)) if want_all else out), _squeeze_ld(ld)
-        except UnsupportedShape as e:
-            _not_native(str(e))
-            return None
+        return _run_stack(self._native_stack(), x, want_all, inverse)
 
     def transform(self, x):
         """Final output and log-det only -- (zs[-1], cum_log_det) without
@@ -361,23 +356,11 @@ class NvpCouplingLayer(nn.Module):
     def _native(self, x, inverse):
         if not _native_eligible([self], x):
             return None
-        from cnf_hip._lib import UnsupportedShape
         from cnf_hip.engine import CouplingStack
-        strict = STRICT_NAN if self.strict_nan is None else bool(self.strict_nan)
+        strict = _strict(self)
         if self._stack is None or self._stack.strict_nan != strict:
             self._stack = CouplingStack([self], strict_nan=strict)
-        try:
-            if _needs_grad(x, self):
-                if inverse:  # cnf_vjp_inverse (strict_nan included)
-                    z, ld = self._stack.inverse_autograd(x, want_all=False)
-                else:
-                    z, ld = self._stack.forward_autograd(x, want_all=False)
-            else:
-                z, ld, _ = self._stack.run(x, inverse=inverse)
-            return z, _squeeze_ld(ld)
-        except UnsupportedShape as e:
-            _not_native(str(e))
-            return None
+        return _run_stack(self._stack, x, False, inverse)
 
     def forward(self, x):
         out = self._native(x, inverse=False)

@@ -65,3 +65,60 @@ def test_stack_adam_matches_torch_adam(D, L, hidden, wd):
     z1, _ = fa.transform(x)
     z2, _ = fb.transform(x)
     assert ((z1 - z2).abs() / (z2.abs() + 1)).max().item() <= 1e-5
+
+
+def test_desc_entry_points_match_tensor_list():
+    """The three cnf_desc Adam entry points against cnf_adam_step_tensors over
+    the same tensor list, through ctypes on copies of one state (parameters,
+    a flat gradient, moments from one prior step): StackAdam steps every stack
+    through cnf_adam_step_tensors, so this is the device run of cnf_adam_step,
+    _sched and _guarded.  Same kernel, same grid: parameters and both moments
+    equal bit for bit; a raised skip flag moves nothing."""
+    import ctypes
+
+    from cnf_hip import _lib
+    from cnf_hip.stack import _ptr, _stream
+
+    stack = _flow(3, 2, [3, 3], seed=3).to(DEV)._native_stack()
+    ps0 = [p.detach().clone() for p in stack.param_tensors()]
+    n = stack.param_count()
+    g = torch.Generator(device=DEV).manual_seed(4)
+    grad = torch.randn(n, device=DEV, generator=g) * 0.1
+    g1 = torch.randn(n, device=DEV, generator=g) * 0.1  # the prior step's gradient
+    m0, v0 = 0.1 * g1, 0.001 * g1 * g1
+    hp = [ctypes.c_double(v) for v in (0.9, 0.999, 1e-8, 0.01)]
+    step, lr = ctypes.c_int64(2), ctypes.c_double(3e-3)
+    sched = torch.tensor([3e-3 / (1 - 0.9 ** 2), (1 - 0.999 ** 2) ** 0.5], device=DEV)
+    flags = [torch.tensor([f], dtype=torch.int32, device=DEV) for f in (0, 1)]
+    lib, desc, st = _lib.lib(), ctypes.byref(stack.desc), _stream(torch.device(DEV))
+    numel = (ctypes.c_int64 * len(ps0))(*[p.numel() for p in ps0])
+
+    def run(call):
+        ps = [p.clone() for p in ps0]
+        m, v = m0.clone(), v0.clone()
+        arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
+        _lib.check("adam", call(arr, _ptr(grad), _ptr(m), _ptr(v)))
+        torch.cuda.synchronize()
+        return ps + [m, v]
+
+    def tensors(sched_t, skip_t):
+        return run(lambda arr, g_, m, v: lib.cnf_adam_step_tensors(
+            ctypes.c_int32(len(ps0)), numel, arr, g_, m, v, step, lr, _ptr(sched_t), *hp,
+            _ptr(skip_t), st))
+
+    def same(a, b):
+        return all(torch.equal(s, t) for s, t in zip(a, b))
+
+    plain = run(lambda arr, g_, m, v: lib.cnf_adam_step(desc, arr, g_, m, v, step, lr, *hp, st))
+    assert same(plain, tensors(None, None))
+    assert not same(plain, ps0 + [m0, v0])  # the step moved the state
+    sch = run(lambda arr, g_, m, v: lib.cnf_adam_step_sched(desc, arr, g_, m, v, _ptr(sched),
+                                                            *hp, st))
+    assert same(sch, tensors(sched, None))
+    for flag in flags:
+        guarded = run(lambda arr, g_, m, v: lib.cnf_adam_step_guarded(
+            desc, arr, g_, m, v, step, lr, None, *hp, _ptr(flag), st))
+        assert same(guarded, tensors(None, flag))
+    assert same(guarded, ps0 + [m0, v0])  # flag 1: nothing moves
+    assert same(run(lambda arr, g_, m, v: lib.cnf_adam_step_guarded(
+        desc, arr, g_, m, v, step, lr, None, *hp, _ptr(flags[0]), st)), plain)
