@@ -52,7 +52,7 @@ EXPORTS = (
     "cnf_radial_param_count", "cnf_radial_workspace_bytes", "cnf_radial_forward",
     "cnf_radial_forward_loss", "cnf_radial_predict", "cnf_radial_score", "cnf_radial_vjp",
     "cnf_radial_loss_vjp",
-    "cnf_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
+    "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
 
@@ -163,6 +163,7 @@ def _bind(lib):
         "cnf_radial_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P, P,
                                                I64, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
+        "cnf_vjp_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),
         "cnf_abi_version": (ctypes.c_int, []),

@@ -110,6 +110,11 @@ class CouplingStack(Stack):
         name = _lib.lib().cnf_kernel_name(ctypes.byref(self.desc)).decode()
         return "valu-fused" if all_outputs and name == "sgpr-fused" else name
 
+    def vjp_kernel_name(self):
+        """Reverse-mode path of cnf_vjp / cnf_loss_vjp for this stack: "vjp2",
+        "vjp-rows", "layerwise", "wide-fused" or "none" (cnf_vjp_kernel_name)."""
+        return _lib.lib().cnf_vjp_kernel_name(ctypes.byref(self.desc)).decode()
+
     def has_native_vjp(self):
         """True when cnf_vjp serves this descriptor (every shape within the
         ABI's limits, strict_nan included, except strict stacks under the legacy

@@ -351,4 +351,10 @@ const char* cnf_kernel_name(const cnf_desc* desc) {
   return sgpr_enabled(s) ? "sgpr-fused" : "valu-fused";
 }
 
+const char* cnf_vjp_kernel_name(const cnf_desc* desc) {
+  Shape s;
+  if (derive_shape(desc, &s) != CNF_OK) return "none";
+  return vjp_path_name(s);
+}
+
 }  // extern "C"

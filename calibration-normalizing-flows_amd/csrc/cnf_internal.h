@@ -205,6 +205,7 @@ inline int64_t wide16_tbits_words(int64_t B) { return (B + 31) / 32 * 512; }  //
 
 // layer-at-a-time MFMA reverse mode of the tile family (cnf_wvjp.hip)
 bool wvjp_ok(const Shape& s);
+bool wvjp_fused16(const Shape& s);  // ... through the fused wide sweeps (at B = 1)
 int wvjp_workspace(const Shape& s, int64_t B, size_t* bytes);
 int wvjp_inv_workspace(const Shape& s, int64_t B, size_t* bytes);
 int wvjp_run(const Shape& s, const void* prepared, const float* x, const int64_t* y,
@@ -218,6 +219,8 @@ int wvjp_inv_run(const Shape& s, const void* prepared, const float* z, const flo
                  void* ws, size_t ws_bytes, hipStream_t st);
 
 int vjp_workspace(const Shape& s, int64_t B, size_t* bytes);
+// "vjp2", "vjp-rows", "layerwise", "wide-fused" or "none" (cnf_vjp_kernel_name)
+const char* vjp_path_name(const Shape& s);
 bool vjp2_ok(const Shape& s);  // the packed-pair SGPR reverse-mode kernel serves this shape
 // kind < 0: generic VJP from gz / gz_all / gld;  kind = CNF_LOSS_*: fused loss
 int vjp_run(const Shape& s, const void* prepared, const float* x, const int64_t* y,

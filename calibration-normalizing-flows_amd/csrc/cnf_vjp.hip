@@ -652,6 +652,16 @@ int reduce_partials(const float* partials, int nblk, int PS, int P, float* grads
 
 bool vjp2_ok(const Shape& s) { return find_v2(s) != nullptr; }
 
+const char* vjp_path_name(const Shape& s) {
+  switch (vjp_path(s)) {
+    case VjpPath::kV2: return "vjp2";
+    case VjpPath::kRows: return "vjp-rows";
+    case VjpPath::kLayerwise: return wvjp_fused16(s) ? "wide-fused" : "layerwise";
+    case VjpPath::kNone: break;
+  }
+  return "none";
+}
+
 // workspace of k_vjp2: [per-wave partials][x_T stash], the stash 256-B aligned
 size_t v2_stash_offset(const Shape& s, int64_t nblk) {
   return ((size_t)(nblk > 0 ? nblk : 1) * partial_stride(s) * 4 + 255) / 256 * 256;

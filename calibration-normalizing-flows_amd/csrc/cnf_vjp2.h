@@ -24,7 +24,8 @@ struct VArgs2 {
   const float* gld;
   float* dx;
   float* partials;
-  float* stash;  // [L][B][D/2] transformed-half layer inputs, (row 2i, row 2i+1) interleaved
+  // [L][B rounded up to even][D/2] transformed-half layer inputs, (row 2i, row 2i+1) interleaved
+  float* stash;
   int64_t B;
   int L, kind;
   float det, grad_scale;
@@ -385,6 +386,10 @@ __global__ __launch_bounds__(64, kV2WPS) void k_vjp2(const float* __restrict__ W
   constexpr int kStage = 32 * kV2SS;
   const int lane = threadIdx.x;
   const int64_t B = a.B;
+  // a layer's rows in the stash: B rounded up to even, so the last lane's pair
+  // slot of an odd batch (2 DT floats, the odd row's half unused) stays inside
+  // its own layer instead of overlapping row 0 of the next one
+  const int64_t BS = (B + 1) & ~(int64_t)1;
   const int L = a.L;
   const int ntiles = (int)((B + kV2TR - 1) / kV2TR);
   const f2 zero = splat(0.f, f2{});
@@ -439,9 +444,9 @@ __global__ __launch_bounds__(64, kV2WPS) void k_vjp2(const float* __restrict__ W
       for (int k = 0; k < DC; ++k) c[k] = v[R<D, O>(DT + k)];
       f2 h1[H1 ? H1 : 1], h2[H2 ? H2 : 1], t[DT], sv[DT];
       {  // x_T of this layer, rows r, r+1
-        // row-major [L][B][DT]: 2*DT contiguous floats as (row r, row r+1)
+        // row-major [L][BS][DT]: 2*DT contiguous floats as (row r, row r+1)
         // pairs (8-B stores: the lane's slot starts 8-B aligned)
-        float* sp = a.stash + ((int64_t)l * B + r) * DT;
+        float* sp = a.stash + ((int64_t)l * BS + r) * DT;
         if (full) {
 #pragma unroll
           for (int j = 0; j < DT; ++j) reinterpret_cast<f2*>(sp)[j] = v[R<D, O>(j)];
@@ -612,7 +617,7 @@ __global__ __launch_bounds__(64, kV2WPS) void k_vjp2(const float* __restrict__ W
       for (int j = 0; j < DT; ++j) gT[j] = g[R<D, Oi>(j)];
       f2 xT[DT];
       {
-        const float* sp = a.stash + ((int64_t)l * B + r) * DT;
+        const float* sp = a.stash + ((int64_t)l * BS + r) * DT;
         if (full) {
 #pragma unroll
           for (int j = 0; j < DT; ++j) xT[j] = reinterpret_cast<const f2*>(sp)[j];

@@ -1409,6 +1409,13 @@ int wvjp_workspace(const Shape& s, int64_t B, size_t* bytes) {
   return CNF_OK;
 }
 
+// the fused training sweeps (plan16) serve this shape's reverse mode at B = 1
+bool wvjp_fused16(const Shape& s) {
+  WTrain16Layout lay;
+  Plan16 p16;
+  return wvjp_ok(s) && plan16(s, 1, &lay, &p16);
+}
+
 // the inverse transform's reverse mode always runs layer at a time
 int wvjp_inv_workspace(const Shape& s, int64_t B, size_t* bytes) {
   if (!wvjp_ok(s)) return CNF_ERR_UNSUPPORTED;

@@ -560,6 +560,15 @@ int cnf_radial_loss_vjp(int32_t dim, int32_t n_layers, const float* const* param
  * wide shapes, every-layer outputs of wide stacks). */
 const char* cnf_kernel_name(const cnf_desc* desc);
 
+/* Which reverse-mode path serves cnf_vjp / cnf_loss_vjp for this descriptor
+ * (host only, no launch): "vjp2" (packed-pair scalar-weight kernel, one launch),
+ * "vjp-rows" (row-resident kernel, one launch), "layerwise" (layer-at-a-time
+ * MFMA sweeps), "wide-fused" (the fused training sweeps of the mfma-wide
+ * shapes; judged at B = 1, a tape beyond the sweeps' limit runs layerwise) or
+ * "none" (cnf_vjp_workspace_bytes returns CNF_ERR_UNSUPPORTED, and for an
+ * invalid descriptor). */
+const char* cnf_vjp_kernel_name(const cnf_desc* desc);
+
 const char* cnf_strerror(int status);
 /* The hipError_t behind the last CNF_ERR_HIP on this thread. */
 int cnf_last_hip_error(void);

@@ -65,6 +65,25 @@ def test_kernel_family_selection():
     assert name(_lib.make_desc(10, 3, [4, 6, 3])) == "mfma-tile"
 
 
+def test_vjp_kernel_selection():
+    """cnf_vjp_kernel_name: the reverse-mode path vjp_path() takes (host only);
+    tests/test_table_sync_cpu.py holds every table shape to the rule."""
+    name = lambda d: _lib.lib().cnf_vjp_kernel_name(ctypes.byref(d)).decode()
+    assert name(_lib.make_desc(10, 6, [5, 5])) == "vjp2"
+    assert name(_lib.make_desc(10, 12, [5, 5])) == "vjp-rows"        # L > 8
+    assert name(_lib.make_desc(10, 6, [5, 5], shift=0)) == "vjp-rows"
+    assert name(_lib.make_desc(10, 5, [10, 10])) == "vjp-rows"
+    assert name(_lib.make_desc(10, 6, [10, 10])) == "layerwise"      # k_vjp's LDS past 64 KB
+    assert name(_lib.make_desc(10, 6, [5, 5], strict_nan=1)) == "layerwise"
+    assert name(_lib.make_desc(10, 3, [4, 6, 3])) == "layerwise"
+    assert name(_lib.make_desc(100, 12, [100, 100])) == "wide-fused"
+    assert name(_lib.make_desc(100, 12, [100, 100], options=_lib.OPT_NO_WIDE)) == "layerwise"
+    assert name(_lib.make_desc(256, 2, [512])) == "none"
+    assert _vjp_bytes(_lib.make_desc(256, 2, [512]), 1)[0] == -3
+    stack = CouplingStack([NvpCouplingLayer(10, [5, 5]) for _ in range(3)])
+    assert stack.vjp_kernel_name() == "vjp2"
+
+
 def test_legacy_kernel_family_selection():
     """Legacy stacks (CNF_OPT_ALT_MASK / S_TANH) of k_valu's shapes run on k_valu
     (never on k_sgpr), the rest on the MFMA-tile family."""

@@ -75,6 +75,7 @@ int main(int argc, char** argv) {
     const int s1 = cnf_prepared_bytes(&d, &bytes);
     EXPECT(is_status(s1));
     EXPECT(cnf_kernel_name(&d) != nullptr);
+    EXPECT(cnf_vjp_kernel_name(&d) != nullptr);
     const int64_t B = U(0, 4) == 0 ? -U(1, 9) : (int64_t)U(0, 1 << 20);
     EXPECT(is_status(cnf_forward_loss_workspace_bytes(&d, B, &ws)));
     EXPECT(is_status(cnf_vjp_workspace_bytes(&d, B, &ws)));
