@@ -46,10 +46,12 @@ EXPORTS = (
     "cnf_scaling_sums_words", "cnf_scaling_workspace_bytes", "cnf_scaling_loss_grad",
     "cnf_scaling_predict",
     "cnf_pav_predict",
-    "cnf_planar_param_count", "cnf_planar_workspace_bytes", "cnf_planar_forward",
+    "cnf_planar_param_count", "cnf_planar_workspace_bytes", "cnf_planar_launch_plan",
+    "cnf_planar_forward",
     "cnf_planar_forward_loss", "cnf_planar_predict", "cnf_planar_score", "cnf_planar_vjp",
     "cnf_planar_loss_vjp",
-    "cnf_radial_param_count", "cnf_radial_workspace_bytes", "cnf_radial_forward",
+    "cnf_radial_param_count", "cnf_radial_workspace_bytes", "cnf_radial_launch_plan",
+    "cnf_radial_forward",
     "cnf_radial_forward_loss", "cnf_radial_predict", "cnf_radial_score", "cnf_radial_vjp",
     "cnf_radial_loss_vjp",
     "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
@@ -135,6 +137,7 @@ def _bind(lib):
         "cnf_planar_param_count": (ctypes.c_int, [I32, I32, ctypes.POINTER(I64)]),
         "cnf_planar_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_planar_launch_plan": (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I32)]),
         "cnf_planar_forward": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, I64, P,
                                               ctypes.c_size_t, P]),
         "cnf_planar_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P,
@@ -150,6 +153,7 @@ def _bind(lib):
         "cnf_radial_param_count": (ctypes.c_int, [I32, I32, ctypes.POINTER(I64)]),
         "cnf_radial_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_radial_launch_plan": (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I32)]),
         "cnf_radial_forward": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I64, P,
                                               ctypes.c_size_t, P]),
         "cnf_radial_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, P, P,

@@ -47,6 +47,22 @@ def workspace_bytes(family, dim, n_layers, B):
     return n.value
 
 
+PLAN_FIELDS = ("lpr", "cpl", "regt", "rega", "gacc", "fwd_blocks", "bwd_blocks", "bwd_units")
+
+
+def launch_plan(family, dim, n_layers, B):
+    """What a call of this shape launches (cnf_<family>_launch_plan, host only):
+    a dict of PLAN_FIELDS -- the row geometry <lpr, cpl> of the forward,
+    predict and score kernels, the reverse kernel's <regt, rega>, whether the
+    wave records sit in the workspace (gacc), and the grids."""
+    fn = "cnf_%s_launch_plan" % family
+    out = (ctypes.c_int32 * 8)()
+    st = getattr(_lib.lib(), fn)(ctypes.c_int32(dim), ctypes.c_int32(n_layers), ctypes.c_int64(B),
+                                 out)
+    _lib.check(fn, st)
+    return dict(zip(PLAN_FIELDS, out))
+
+
 def param_count(family, dim, n_layers):
     fn = "cnf_%s_param_count" % family
     n = ctypes.c_int64()
@@ -100,6 +116,10 @@ class RowStack(Stack):
 
     def param_count(self):
         return self.L * sum(self.sizes(self.dim))
+
+    def launch_plan(self, B):
+        """The kernels and grids a call on B rows takes (rowstack.launch_plan)."""
+        return launch_plan(self.family, self.dim, self.L, B)
 
     def reserve_workspace(self, B, device):
         """Hold one private workspace for batches up to B rows on `device`,

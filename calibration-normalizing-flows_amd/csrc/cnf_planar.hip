@@ -55,7 +55,13 @@ struct Ptrs {
 
 // per layer: the constant record [w | u_hat | 8 scalars], 2 D + 2 row sums
 Geo planar_geometry(int D, int L) { return geometry(D, L, 2 * padded_dim(D) + 8, 2 * D + 2); }
-constexpr RowFamily kFamily{kMaxL, planar_geometry};
+// reverse mode: the tape in registers up to kRegL layers; per-lane accumulators
+// on top of it for one-lane rows of at most kAccD columns
+constexpr BwdVariant planar_bwd_variant(int lpr, int cpl, int L) {
+  const bool regt = L <= kRegL;
+  return {regt, regt && lpr == 1 && cpl <= kAccD};
+}
+constexpr RowFamily kFamily{kMaxL, planar_geometry, planar_bwd_variant};
 
 // ---- per-layer constants --------------------------------------------------
 
@@ -608,12 +614,13 @@ void launch_score(int blocks, hipStream_t s, const float* x, const float* blob, 
 
 template <int LPR, int CPL>
 void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (a.L > kRegL) {
+  if (!planar_bwd_variant(LPR, CPL, a.L).regt) {
     hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
                        a);
     return;
   }
-  if constexpr (LPR == 1 && CPL <= kAccD) {
+  // rega depends on the depth through regt alone: the geometry's answer at kRegL
+  if constexpr (planar_bwd_variant(LPR, CPL, kRegL).rega) {
     hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
                        a);
   } else {
@@ -785,6 +792,10 @@ extern "C" int cnf_planar_param_count(int32_t dim, int32_t n_layers, int64_t* n_
 extern "C" int cnf_planar_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
                                           size_t* bytes) {
   return cnf::rowflow::workspace_bytes(cnf::kFamily, dim, n_layers, B, bytes);
+}
+
+extern "C" int cnf_planar_launch_plan(int32_t dim, int32_t n_layers, int64_t B, int32_t out[8]) {
+  return cnf::rowflow::launch_plan(cnf::kFamily, dim, n_layers, B, out);
 }
 
 extern "C" int cnf_planar_forward(int32_t dim, int32_t n_layers, const float* const* params,

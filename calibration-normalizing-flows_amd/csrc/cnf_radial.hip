@@ -28,9 +28,11 @@
 // in registers up to kRegL layers, in an [L][B] tape in the workspace above.
 // Because 1 + beta h = (r + sp) / (a + r), the backward sweep rebuilds
 // d_l = (z_l - z0_l) (a + r) / (r + sp) and x_l = z0_l + d_l; r + sp > 0 for
-// every finite b.  The D + 2 row sums per layer (sum g_d [D], g_beta, sum g_r)
-// live in per-lane accumulators over the whole grid-stride loop when one lane
-// holds a row and L <= kRegL (one wave sum at the end); otherwise each pass
+// every finite b.  Each inversion multiplies the rebuilt row's error by
+// (a + r) / (r + sp), so above kRegL layers the row is run forward again from
+// the input every kRebuild layers.
+// The D + 2 row sums per layer (sum g_d [D], g_beta, sum g_r) live in per-lane
+// accumulators over the whole grid-stride loop when one lane holds a row and L <= kRegL (one wave sum at the end); otherwise each pass
 // ends in a wave sum per word that one fixed lane adds into the wave's record
 // (LDS, or the workspace when 4 records exceed 48 KB).  Block (or wave) records
 // go to the workspace; k_radial_finish adds them in index order, applies the
@@ -55,6 +57,7 @@ using namespace rowflow;
 using valu::wave_sum_dpp63;
 
 constexpr int kMaxL = CNF_RADIAL_MAX_LAYERS;
+constexpr int kRebuild = 16;  // workspace-tape reverse mode: longest chain of layer inversions
 
 struct Ptrs {
   const float* p[3 * kMaxL];
@@ -62,7 +65,13 @@ struct Ptrs {
 
 // per layer: the constant record [z0 | 8 scalars], D + 2 row sums
 Geo radial_geometry(int D, int L) { return geometry(D, L, padded_dim(D) + 8, D + 2); }
-constexpr RowFamily kFamily{kMaxL, radial_geometry};
+// reverse mode: the tape in registers up to kRegL layers; per-lane accumulators
+// on top of it for every one-lane row
+constexpr BwdVariant radial_bwd_variant(int lpr, int /*cpl*/, int L) {
+  const bool regt = L <= kRegL;
+  return {regt, regt && lpr == 1};
+}
+constexpr RowFamily kFamily{kMaxL, radial_geometry, radial_bwd_variant};
 
 // ---- per-layer constants --------------------------------------------------
 
@@ -508,6 +517,20 @@ __global__ __launch_bounds__(kThreads) void k_radial_bwd(BwdArgs A) {
             if (c < D) g[k] += A.gz_all[((int64_t)(l - 1) * B + row) * D + c];
           }
         }
+        // Inverting a layer multiplies the error of the rebuilt row by
+        // 1 / (1 + beta h) >= 1 where the layer contracts, so a deep
+        // contracting stack loses the early layers' inputs (2e-3 absolute
+        // after 64 layers at D = 3).  Every kRebuild layers the row is run
+        // forward again from the input instead: the chain of inversions stays
+        // at most kRebuild long.  Block-uniform bounds.
+        if (l > 0 && l % kRebuild == 0) {
+#pragma unroll
+          for (int k = 0; k < CPL; ++k) {
+            const int c = gl + LPR * k;
+            xv[k] = (valid && c < D) ? A.x[row * D + c] : 0.f;
+          }
+          for (int j = 0; j < l; ++j) radial_step<LPR, CPL>(xv, blob + (size_t)j * cs, gl);
+        }
       }
     }
     if (A.dx && valid) {
@@ -629,12 +652,13 @@ void launch_predict(int blocks, hipStream_t s, const float* x, const float* blob
 
 template <int LPR, int CPL>
 void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (a.L > kRegL) {
+  if (!radial_bwd_variant(LPR, CPL, a.L).regt) {
     hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
                        a);
     return;
   }
-  if constexpr (LPR == 1) {
+  // rega depends on the depth through regt alone: the geometry's answer at kRegL
+  if constexpr (radial_bwd_variant(LPR, CPL, kRegL).rega) {
     hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
                        a);
   } else {
@@ -791,6 +815,10 @@ extern "C" int cnf_radial_param_count(int32_t dim, int32_t n_layers, int64_t* n_
 extern "C" int cnf_radial_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
                                           size_t* bytes) {
   return cnf::rowflow::workspace_bytes(cnf::kFamily, dim, n_layers, B, bytes);
+}
+
+extern "C" int cnf_radial_launch_plan(int32_t dim, int32_t n_layers, int64_t B, int32_t out[8]) {
+  return cnf::rowflow::launch_plan(cnf::kFamily, dim, n_layers, B, out);
 }
 
 extern "C" int cnf_radial_forward(int32_t dim, int32_t n_layers, const float* const* params,

@@ -191,10 +191,20 @@ inline int check_shape(int32_t dim, int32_t n_layers, int max_layers) {
   return CNF_OK;
 }
 
-// A family: its layer cap and its geometry(D, L, cs, ps) with cs and ps filled in.
+// Which instantiation of a family's reverse-mode kernel a launch takes: regt,
+// the tape in registers (L <= kRegL); rega, per-lane accumulators on top of it
+// (the family says for which geometries).  One helper per family answers it,
+// for launch_bwd and for cnf_<family>_launch_plan alike.
+struct BwdVariant {
+  bool regt, rega;
+};
+
+// A family: its layer cap, its geometry(D, L, cs, ps) with cs and ps filled in,
+// and its reverse-mode variant for a geometry and depth.
 struct RowFamily {
   int max_layers;
   Geo (*geo)(int D, int L);
+  BwdVariant (*bwd)(int lpr, int cpl, int L);
 };
 
 // Common argument checks; fills the pointer table (3 * max_layers entries,
@@ -227,6 +237,27 @@ inline int workspace_bytes(const RowFamily& f, int32_t dim, int32_t n_layers, in
   if (st != CNF_OK) return st;
   if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
   *bytes = (size_t)plan(f.geo(dim, n_layers), n_layers, B).total * sizeof(float);
+  return CNF_OK;
+}
+
+// the body of cnf_<family>_launch_plan: what a call of this shape would launch,
+// from the functions the launches themselves use.  Host only.
+inline int launch_plan(const RowFamily& f, int32_t dim, int32_t n_layers, int64_t B,
+                       int32_t* out) {
+  if (!out) return CNF_ERR_NULL;
+  const int st = check_shape(dim, n_layers, f.max_layers);
+  if (st != CNF_OK) return st;
+  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
+  const Geo g = f.geo(dim, n_layers);
+  const BwdVariant v = f.bwd(g.lpr, g.cpl, n_layers);
+  out[0] = g.lpr;
+  out[1] = g.cpl;
+  out[2] = v.regt ? 1 : 0;
+  out[3] = v.rega ? 1 : 0;
+  out[4] = g.gacc ? 1 : 0;
+  out[5] = fwd_blocks(g, B);
+  out[6] = bwd_blocks(g, B);
+  out[7] = bwd_units(g, B);
   return CNF_OK;
 }
 

@@ -401,6 +401,16 @@ int cnf_pav_predict(const float* x, int32_t dim, int64_t B, const double* thr_x,
 /* 3 * L tensors, L * (2 D + 1) floats. */
 int cnf_planar_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats);
 int cnf_planar_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B, size_t* bytes);
+/* What a call of this shape launches (host only, no launch; argument errors as
+ * cnf_planar_workspace_bytes), computed by the functions the launches use:
+ *   out = {LPR, CPL (columns per lane, DP / LPR), regt, rega, gacc,
+ *          forward blocks F, reverse blocks, reverse records U}
+ * regt: the reverse mode keeps its tape in registers (L <= 10); rega: and its
+ * row sums in per-lane accumulators (LPR == 1, D <= 11); gacc: the wave
+ * records live in the workspace (PW > 3072).  The forward, predict and score
+ * kernels are the <LPR, CPL> instantiation, the reverse kernel <LPR, CPL, regt,
+ * rega>.  The block counts at B == 0 are those of B == 1 (no kernel runs). */
+int cnf_planar_launch_plan(int32_t dim, int32_t n_layers, int64_t B, int32_t out[8]);
 
 /* Flow.forward of the stack: z [B][D] (= zs[-1]), logdet [B] (the sum over
  * layers), z_all [L][B][D] (the zs list); each may be NULL. */
@@ -499,6 +509,8 @@ int cnf_planar_loss_vjp(int32_t dim, int32_t n_layers, const float* const* param
 /* 3 * L tensors, L * (D + 2) floats. */
 int cnf_radial_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats);
 int cnf_radial_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B, size_t* bytes);
+/* As cnf_planar_launch_plan; rega: LPR == 1 at L <= 10, whatever the width. */
+int cnf_radial_launch_plan(int32_t dim, int32_t n_layers, int64_t B, int32_t out[8]);
 
 /* Flow.forward of the stack: z [B][D] (= zs[-1]) and z_all [L][B][D] (the zs
  * list); each may be NULL. */
@@ -539,8 +551,10 @@ int cnf_radial_score(int32_t dim, int32_t n_layers, const float* const* params, 
  * (each may be NULL = zero); writes grads [cnf_radial_param_count] (per layer
  * z0, a, b; overwritten) and dx [B][D] (may be NULL).  The forward pass is
  * recomputed inside; the only tape is one r per (row, layer), from which a
- * layer's input is rebuilt as z0 + (z - z0) (a + r) / (r + sp).  The norm's
- * gradient is 0 where r == 0, as torch's. */
+ * layer's input is rebuilt as z0 + (z - z0) (a + r) / (r + sp); above 10
+ * layers the row is also run forward again from x every 16 layers, so no input
+ * comes out of more than 16 such inversions.  The norm's gradient is 0 where
+ * r == 0, as torch's. */
 int cnf_radial_vjp(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
                    const float* gz, const float* gz_all, float* grads, float* dx, int64_t B,
                    void* workspace, size_t workspace_bytes, void* stream);

@@ -193,8 +193,8 @@ def test_cpu_calibrator_fit_matches_reference_run():
 def test_exports_match_header():
     names = [n for n in _lib.EXPORTS if n.startswith("cnf_radial_")]
     assert sorted(names) == sorted("cnf_radial_" + s for s in (
-        "param_count", "workspace_bytes", "forward", "forward_loss", "vjp", "loss_vjp", "predict",
-        "score"))
+        "param_count", "workspace_bytes", "launch_plan", "forward", "forward_loss", "vjp",
+        "loss_vjp", "predict", "score"))
     lib = _lib.lib()
     assert all(hasattr(lib, n) for n in names)
 
