@@ -20,7 +20,9 @@ replica, and `evaluate` copies only the 4 + 3 * bins record words to the host.
 CNF_PLANAR_NATIVE=0 keeps a planar flow on torch ops throughout.
 A flow made of RadialLayers (flows._factory.RadialFlow) takes the same route
 on the cnf_radial_* kernels -- cnf_radial_loss_vjp, cnf_radial_forward_loss,
-cnf_radial_predict, cnf_radial_score; its `history['log_det']` is zeros, the
+cnf_radial_predict, cnf_radial_score (and a flow made of AffineConstantLayers,
+flows._factory.AffineConstantFlow, on the cnf_affine_* ones, its log-det one
+number per batch); a radial flow's `history['log_det']` is zeros, the
 layer's log-det being the reference's constant 0 -- and CNF_RADIAL_NATIVE=0
 keeps it on torch ops.
 Any other flow (or a CPU device) runs the reference's own torch loop.
@@ -44,8 +46,9 @@ per-class tables and returns a ROCm fp32 tensor.  (The fit itself is not on
 the device yet: DESIGN.md section 7d.)
 
 `Calibrator.score` / `score_sums` is the one scoring interface of every
-calibrator.  A planar or radial TorchFlowCalibrator scores in ONE fused launch
-that never stores the probabilities (cnf_planar_score, cnf_radial_score).  DummyCalibrator (whose predict
+calibrator.  A planar, radial or affine TorchFlowCalibrator scores in ONE fused
+launch that never stores the probabilities (cnf_planar_score, cnf_radial_score,
+cnf_affine_score).  DummyCalibrator (whose predict
 now also runs on the device), the four scaling calibrators, PAVCalibrator and
 a coupling flow score a ROCm tensor with their fused predict plus one
 cnf_metrics launch; host inputs go through predict() and the record of
@@ -460,11 +463,13 @@ def _native_stack(flow, dev, need_vjp=True):
 
 
 def _tensor_stack(flow, dev):
-    """The fused PlanarStack or RadialStack behind `flow` (the stacks without a
-    cnf_desc, whose parameters StackAdam steps as a tensor list), or None when
-    the flow is not an all-planar or all-radial Flow with fp32 parameters on
-    the ROCm device `dev`, the shape is outside the kernels' envelope, or the
-    family's switch (CNF_PLANAR_NATIVE=0 / CNF_RADIAL_NATIVE=0) is off."""
+    """The fused PlanarStack, RadialStack or AffineStack behind `flow` (the
+    stacks without a cnf_desc, whose parameters StackAdam steps as a tensor
+    list), or None when the flow is not an all-planar, all-radial or all-affine
+    Flow with fp32 parameters on the ROCm device `dev` (an affine layer needs
+    both of its parameters), the shape is outside the kernels' envelope, or the
+    family's switch (CNF_PLANAR_NATIVE=0 / CNF_RADIAL_NATIVE=0 /
+    CNF_AFFINE_NATIVE=0) is off."""
     if torch.device(dev).type != "cuda":
         return None
     try:
@@ -475,7 +480,8 @@ def _tensor_stack(flow, dev):
         return None
     for family, native, layer, max_layers in (
             ("planar", F.PLANAR_NATIVE, F.PlanarLayer, _lib.PLANAR_MAX_LAYERS),
-            ("radial", F.RADIAL_NATIVE, F.RadialLayer, _lib.RADIAL_MAX_LAYERS)):
+            ("radial", F.RADIAL_NATIVE, F.RadialLayer, _lib.RADIAL_MAX_LAYERS),
+            ("affine", F.AFFINE_NATIVE, F.AffineConstantLayer, _lib.AFFINE_MAX_LAYERS)):
         if not native or not isinstance(flow, F.Flow):
             continue
         layers = list(flow.layers)
@@ -523,7 +529,7 @@ class _EpochRunner:
     eval pass's fused forward + loss per batch, whose LAST batch's sums are the
     epoch's history terms.
 
-    `stack` is a CouplingStack, a PlanarStack or a RadialStack; the runner uses
+    `stack` is a CouplingStack, a PlanarStack, a RadialStack or an AffineStack; the runner uses
     loss_and_grads(x, y, grad_scale=, grads_out=, terms_out=),
     forward_loss(x, y, terms_out=), reserve_workspace / release_workspace and
     invalidate() (no-ops where a stack has nothing to do).  The flat gradient
@@ -691,8 +697,8 @@ class TorchFlowCalibrator(Calibrator):
         """Same schedule on the fused kernels: one cnf_loss_vjp launch plus one
         cnf_adam_step launch per training batch, one cnf_forward_loss launch per
         evaluation batch (a PlanarStack: cnf_planar_loss_vjp,
-        cnf_adam_step_tensors, cnf_planar_forward_loss; a RadialStack: the
-        cnf_radial_* siblings).  Each pass over the
+        cnf_adam_step_tensors, cnf_planar_forward_loss; a RadialStack or an
+        AffineStack: the cnf_radial_* / cnf_affine_* siblings).  Each pass over the
         data draws its order exactly as
         the reference's DataLoader(shuffle=True) does (_loader_order), so
         minibatch runs see the reference's batches and the eval history keeps
@@ -727,10 +733,11 @@ class TorchFlowCalibrator(Calibrator):
         return _history(terms_all, epochs, N)
 
     def _fit_torch_step(self, stack, logits, target, epochs, batch_size):
-        """The fit of a planar or radial stack under an optimizer the native
+        """The fit of a planar, radial or affine stack under an optimizer the native
         Adam does not reproduce (cnf_hip.adam.supports is false: AdamW,
         amsgrad, ...), every epoch eager: per training batch one fused loss +
-        reverse-mode launch (cnf_planar_loss_vjp / cnf_radial_loss_vjp) whose
+        reverse-mode launch (cnf_planar_loss_vjp / cnf_radial_loss_vjp /
+        cnf_affine_loss_vjp) whose
         flat gradient is viewed into each parameter's .grad, then the torch
         optimizer's own step (its state stays torch's); per evaluation batch
         one fused forward + loss launch.  Every pass draws its order as the
@@ -806,8 +813,8 @@ class TorchFlowCalibrator(Calibrator):
         """Calibrator.predict (calibrators.py:40-44 with predict_post, :330-353):
         centring, the flow, softmax and the prior correction
         softmax(log(p + 1e-7) - log_priors).  On a ROCm device this is ONE fused
-        launch (cnf_predict; cnf_planar_predict / cnf_radial_predict for a
-        planar / radial flow) on a
+        launch (cnf_predict; cnf_planar_predict / cnf_radial_predict /
+        cnf_affine_predict for a planar / radial / affine flow) on a
         resident replica of the flow, with one H2D copy of the logits and one
         D2H copy of the probabilities."""
         probs = self._predict_device(logits)
@@ -838,8 +845,9 @@ class TorchFlowCalibrator(Calibrator):
 
     def score_sums(self, logits, target, bins=15, record=None):
         """evaluate_sums' record (logits: arrays or tensors, ROCm ones
-        included).  A planar or radial flow on a ROCm device scores in ONE
-        cnf_planar_score / cnf_radial_score launch on the resident replica; a
+        included).  A planar, radial or affine flow on a ROCm device scores in
+        ONE cnf_planar_score / cnf_radial_score / cnf_affine_score launch on the
+        resident replica; a
         coupling flow keeps
         its fused predict plus one cnf_metrics launch; without a native stack
         the host path scores predict()'s float64 probabilities."""

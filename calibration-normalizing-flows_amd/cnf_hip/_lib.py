@@ -34,6 +34,7 @@ PLANAR_MAX_LAYERS = 64  # CNF_PLANAR_MAX_LAYERS (cnf_planar_*)
 PLANAR_REG_LAYERS = 10  # deeper stacks keep their tanh tape in the workspace
 RADIAL_MAX_LAYERS = 64  # CNF_RADIAL_MAX_LAYERS (cnf_radial_*)
 RADIAL_REG_LAYERS = 10  # deeper stacks keep their tape of r in the workspace
+AFFINE_MAX_LAYERS = 64  # CNF_AFFINE_MAX_LAYERS (cnf_affine_*)
 
 # Every symbol include/cnf.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -54,6 +55,10 @@ EXPORTS = (
     "cnf_radial_forward",
     "cnf_radial_forward_loss", "cnf_radial_predict", "cnf_radial_score", "cnf_radial_vjp",
     "cnf_radial_loss_vjp",
+    "cnf_affine_param_count", "cnf_affine_workspace_bytes", "cnf_affine_launch_plan",
+    "cnf_affine_forward", "cnf_affine_inverse",
+    "cnf_affine_forward_loss", "cnf_affine_predict", "cnf_affine_score", "cnf_affine_vjp",
+    "cnf_affine_loss_vjp",
     "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -166,6 +171,24 @@ def _bind(lib):
                                           ctypes.c_size_t, P]),
         "cnf_radial_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P, P,
                                                I64, P, ctypes.c_size_t, P]),
+        "cnf_affine_param_count": (ctypes.c_int, [I32, I32, ctypes.POINTER(I64)]),
+        "cnf_affine_workspace_bytes": (ctypes.c_int, [I32, I32, I64,
+                                                      ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_affine_launch_plan": (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I32)]),
+        "cnf_affine_forward": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
+        "cnf_affine_inverse": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
+        "cnf_affine_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, P, P,
+                                                   P, I64, P, ctypes.c_size_t, P]),
+        "cnf_affine_predict": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I64, P,
+                                              ctypes.c_size_t, P]),
+        "cnf_affine_score": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, I32, P, I64, P,
+                                            ctypes.c_size_t, P]),
+        "cnf_affine_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, P, P, P, P, I64, P,
+                                          ctypes.c_size_t, P]),
+        "cnf_affine_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, F, P, P,
+                                               P, I64, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_vjp_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),

@@ -1,5 +1,6 @@
 """What the host sides of the row-wise flow families share (cnf_hip/planar.py,
-cnf_hip/radial.py; csrc/cnf_rowflow.h is the library's counterpart).
+cnf_hip/radial.py, cnf_hip/affine.py; csrc/cnf_rowflow.h is the library's
+counterpart).
 
 `RowStack` binds a run of layers of one family and one width to that family's
 entry points, cnf_<family>_* (include/cnf.h).  Every launching entry point
@@ -7,11 +8,18 @@ takes (dim, n_layers, params, x, ..., B, workspace, bytes, stream); `_call`
 supplies that frame, and a family's launch methods pass what goes between.  A
 subclass declares
 
-  family                "planar" / "radial": the entry-point and `stats` key prefix
+  family                "planar" / "radial" / "affine": the entry-point and `stats`
+                        key prefix
   slot                  the attribute under which a flows.Flow caches its stack
   layer                 the name of its layer class in flows.flows
-  layer_tensors(layer)  the layer's three parameter tensors, in ABI order
-  sizes(D)              their element counts
+  layer_tensors(layer)  the layer's parameter tensors, in ABI order
+  sizes(D)              their element counts (as many as the layer has tensors)
+  param_dims            the dimensions a parameter tensor may have (1-d vectors
+                        and 0-d scalars by default; affine: 2)
+  param_shape(n)        the shape a parameter of n elements must have, or None
+                        for any of param_dims (affine: (1, n))
+  entries               its launching entry points besides the common six
+  has_inverse           whether run(x, inverse=True) exists
 
 and keeps one workspace cache (`_ws_cache`, one buffer per (device, stream)).
 The parameter table, the checks, `split` and the autograd backward are the
@@ -33,9 +41,11 @@ from .stack import Stack, _ptr, _stream, _stream_key, stats
 
 @functools.lru_cache(maxsize=None)
 def stack_class(family):
-    """PlanarStack for "planar", RadialStack for "radial" (a layer's `_family`)."""
-    from . import planar, radial
-    return {"planar": planar.PlanarStack, "radial": radial.RadialStack}[family]
+    """PlanarStack for "planar", RadialStack for "radial", AffineStack for
+    "affine" (a layer's `_family`)."""
+    from . import affine, planar, radial
+    return {"planar": planar.PlanarStack, "radial": radial.RadialStack,
+            "affine": affine.AffineStack}[family]
 
 
 def workspace_bytes(family, dim, n_layers, B):
@@ -72,11 +82,21 @@ def param_count(family, dim, n_layers):
 
 
 class RowStack(Stack):
+    param_dims = (0, 1)
+    entries = ()
+    has_inverse = False
+
+    @staticmethod
+    def param_shape(n):
+        return None
+
     def __init_subclass__(cls):
         # entry -> (entry point, `stats` key): forward_loss counts as a forward
         cls._names = {e: ("cnf_%s_%s" % (cls.family, e),
                           "%s_%s" % (cls.family, "forward" if e == "forward_loss" else e))
-                      for e in ("forward", "forward_loss", "vjp", "loss_vjp", "predict", "score")}
+                      for e in ("forward", "forward_loss", "vjp", "loss_vjp", "predict", "score")
+                      + tuple(cls.entries)}
+        cls._per_layer = len(cls.sizes(1))
 
     def __init__(self, layers):
         self.layers = list(layers)
@@ -99,13 +119,16 @@ class RowStack(Stack):
             return False
         tensors = cls.layer_tensors
         p0 = tensors(layers[0])[0]
-        if not torch.is_tensor(p0) or p0.dim() != 1:
+        if not torch.is_tensor(p0) or p0.dim() != max(cls.param_dims):
             return False
         sizes = cls.sizes(p0.numel())
         dev = p0.device if device is None else torch.device(device)
         for ly in layers:
             for t, n in zip(tensors(ly), sizes):
-                if not torch.is_tensor(t) or t.numel() != n or t.dim() > 1:
+                if not torch.is_tensor(t) or t.numel() != n or t.dim() not in cls.param_dims:
+                    return False
+                shape = cls.param_shape(n)
+                if shape is not None and tuple(t.shape) != shape:
                     return False
                 if t.dtype != torch.float32 or not t.is_contiguous():
                     return False
@@ -150,7 +173,7 @@ class RowStack(Stack):
         fn, counter = self._names[entry]
         B, dev = x.shape[0], x.device
         ws, n = ws
-        ptrs = (ctypes.c_void_p * (3 * self.L))(*[p.data_ptr() for p in self._params])
+        ptrs = (ctypes.c_void_p * (self._per_layer * self.L))(*[p.data_ptr() for p in self._params])
         with torch.cuda.device(dev):
             st = getattr(_lib.lib(), fn)(
                 ctypes.c_int32(self.dim), ctypes.c_int32(self.L), ptrs, _ptr(x), *args,

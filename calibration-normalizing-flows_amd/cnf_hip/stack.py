@@ -1,6 +1,6 @@
 """What every native stack shares: `Stack`, the base of `CouplingStack`
 (cnf_hip/engine.py) and of `RowStack` (cnf_hip/rowstack.py, under
-`PlanarStack` and `RadialStack`), and `StackFn`, the base of their autograd
+`PlanarStack`, `RadialStack` and `AffineStack`), and `StackFn`, the base of their autograd
 Functions.
 
 A stack binds a run of layers to the library's fused launches.  The layers
@@ -8,10 +8,13 @@ keep owning their parameters; the stack lists them once in ABI order
 (`_params`).  Buffers are torch allocations on the input's device and the
 launches go to torch's current stream there.  A subclass sets
 
-  family      "coupling" / "planar" / "radial": the word in the error texts
+  family      "coupling" / "planar" / "radial" / "affine": the word in the error texts
   _rows       what the input check calls its rows
   _fp32_why   why the path is fp32, in the dtype error
   _stale      what a stale backward says changed
+  squeeze_logdet  whether the flow squeezes the stack's log-det as the reference's
+              layers do (torch.sum(..., dim=1).squeeze()); False for a stack whose
+              log-det is one number of shape [1]
 """
 import ctypes
 
@@ -23,7 +26,9 @@ stats = {"forward": 0, "inverse": 0, "prepare": 0, "vjp": 0, "loss_vjp": 0, "pre
          "metrics": 0, "torch_ops": 0, "planar_forward": 0, "planar_vjp": 0,
          "planar_loss_vjp": 0, "planar_predict": 0, "planar_score": 0,
          "radial_forward": 0, "radial_vjp": 0, "radial_loss_vjp": 0, "radial_predict": 0,
-         "radial_score": 0}
+         "radial_score": 0,
+         "affine_forward": 0, "affine_inverse": 0, "affine_vjp": 0, "affine_loss_vjp": 0,
+         "affine_predict": 0, "affine_score": 0}
 
 
 def _ptr(t):
@@ -60,6 +65,7 @@ class Stack:
     _rows = "rows"
     _fp32_why = ""
     _stale = "parameter"
+    squeeze_logdet = True
 
     def param_tensors(self):
         """ABI order (the state_dict order)."""

@@ -1,9 +1,11 @@
-// What the row-wise flow families (cnf_planar.hip, cnf_radial.hip) share: the
-// grid constants, the geometry of a row in lanes, the workspace plan, the
-// argument checks, the shape dispatch and the lane helpers.  A family differs
-// from the other in two geometry words -- cs, the floats of its per-layer
-// constant record, and ps, the row sums per layer of its reverse mode -- which
-// it passes to geometry().
+// What the row-wise flow families (cnf_planar.hip, cnf_radial.hip,
+// cnf_affine.hip) share: the grid constants, the geometry of a row in lanes, the
+// workspace plan, the argument checks, the shape dispatch and the lane helpers.
+// A family differs from the others in three geometry words -- cs, the floats of
+// its per-layer constant record, ps, the row sums per layer of its reverse
+// mode, and tf, the tape floats per (row, layer) its deep stacks keep in the
+// workspace (1, or 0 for a family without such a tape) -- which it passes to
+// geometry(), and in its parameter tensors per layer (RowFamily::tensors).
 //
 // Everything here is either host code or an inline device function that was
 // one already; the kernel bodies stay in their files, because wrapping kernel
@@ -33,7 +35,7 @@ constexpr int64_t kMaxRows = (int64_t)1 << 31;
 // Rows: one lane per row for D <= 16, 16 lanes per row for D <= 64, 64 above;
 // column c of a row sits in lane c % lpr, slot c / lpr (cpl slots, dp = lpr * cpl).
 struct Geo {
-  int lpr, cpl, dp, cs, ps, pw;
+  int lpr, cpl, dp, cs, ps, pw, tf;
   bool gacc;
 };
 
@@ -45,7 +47,7 @@ inline int padded_dim(int D) {
   return (D + lpr - 1) / lpr * lpr;
 }
 
-inline Geo geometry(int D, int L, int cs, int ps) {
+inline Geo geometry(int D, int L, int cs, int ps, int tf = 1) {
   Geo g;
   g.lpr = lanes_per_row(D);
   g.dp = padded_dim(D);
@@ -53,6 +55,7 @@ inline Geo geometry(int D, int L, int cs, int ps) {
   g.cs = cs;
   g.ps = ps;
   g.pw = L * g.ps + 4;
+  g.tf = tf;
   g.gacc = g.pw > kLdsWords;
   return g;
 }
@@ -93,7 +96,7 @@ inline Plan plan(const Geo& g, int L, int64_t B) {
   const int64_t lf = (int64_t)fwd_blocks(g, B) * 4;
   if (lf > pf) pf = lf;
   p.tape = p.part + round64(pf);
-  p.total = p.tape + (L > kRegL ? round64((int64_t)L * B) : 0);
+  p.total = p.tape + (L > kRegL ? round64((int64_t)L * B * g.tf) : 0);
   return p;
 }
 
@@ -199,16 +202,18 @@ struct BwdVariant {
   bool regt, rega;
 };
 
-// A family: its layer cap, its geometry(D, L, cs, ps) with cs and ps filled in,
-// and its reverse-mode variant for a geometry and depth.
+// A family: its layer cap, its geometry(D, L, cs, ps, tf) with the family words
+// filled in, its reverse-mode variant for a geometry and depth, and its
+// parameter tensors per layer.
 struct RowFamily {
   int max_layers;
   Geo (*geo)(int D, int L);
   BwdVariant (*bwd)(int lpr, int cpl, int L);
+  int tensors = 3;
 };
 
-// Common argument checks; fills the pointer table (3 * max_layers entries,
-// null past the 3 * n_layers given), the geometry and the plan.
+// Common argument checks; fills the pointer table (tensors * max_layers
+// entries, null past the tensors * n_layers given), the geometry and the plan.
 inline int check_common(const RowFamily& f, int32_t dim, int32_t n_layers,
                         const float* const* params, const float* x, int64_t B, const void* ws,
                         size_t ws_bytes, const float** table, Geo* g, Plan* p) {
@@ -216,12 +221,13 @@ inline int check_common(const RowFamily& f, int32_t dim, int32_t n_layers,
   if (st != CNF_OK) return st;
   if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
   if (!params) return CNF_ERR_NULL;
-  for (int i = 0; i < 3 * n_layers; ++i) {
+  const int nt = f.tensors;
+  for (int i = 0; i < nt * n_layers; ++i) {
     if (!params[i]) return CNF_ERR_NULL;
     if (mis4(params[i])) return CNF_ERR_ALIGN;
     table[i] = params[i];
   }
-  for (int i = 3 * n_layers; i < 3 * f.max_layers; ++i) table[i] = nullptr;
+  for (int i = nt * n_layers; i < nt * f.max_layers; ++i) table[i] = nullptr;
   *g = f.geo(dim, n_layers);
   *p = plan(*g, n_layers, B);
   if (B > 0 && (!x || !ws || ws_bytes < (size_t)p->total * sizeof(float))) return CNF_ERR_NULL;

@@ -76,7 +76,10 @@ class RadialFlow(Flow):
 
 class AffineConstantFlow(Flow):
     """A Flow of AffineConstantLayers (z = x * exp(s) + t per layer) whose call
-    returns (z_final, log_det).  Torch ops on every device."""
+    returns (z_final, log_det), the log-det of shape [1] as the reference's
+    layers return it.  On a ROCm device one fused launch per call
+    (cnf_affine_forward / cnf_affine_inverse), as the planar and radial
+    factories; layers=5 is the depth of train-flows-det.ipynb."""
 
     def __init__(self, dim, layers=5, **kwargs):
         super().__init__([AffineConstantLayer(dim) for _ in range(layers)])

@@ -6,7 +6,9 @@ flows/flows.py), so `from flows.flows import Flow, NvpCouplingLayer` works
 unchanged.  On a ROCm device a Flow made of NvpCouplingLayers runs as ONE fused
 HIP launch per call (libcnf_hip.so, include/cnf.h), and so does a Flow made of
 PlanarLayers (cnf_planar_*) or of RadialLayers (cnf_radial_*; both forward
-only, neither flow has a tractable inverse):
+only, neither flow has a tractable inverse), and a Flow made of
+AffineConstantLayers that have both parameters (cnf_affine_*: forward and
+inverse, the log-det one number of shape [1] as the reference's):
 
   Flow.forward(x)  -> (zs, cum_log_det)   fused cnf_forward, zs = views of one
                                            [L, B, D] buffer       (flows.py:17-25)
@@ -17,17 +19,19 @@ only, neither flow has a tractable inverse):
 from torch autograd, which calls the native VJP kernel.
 
 Host tensors (CPU) run the same math with torch ops, as the reference does.
-Layers the native engine does not cover (AffineConstantLayer -- out of the
-hot-path scope) and mixed stacks run as torch ops, layer by layer.
-CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops as well, and
-CNF_RADIAL_NATIVE=0 radial ones.  A radial stack's log-det is the reference's
+Layers the native engine does not cover (an AffineConstantLayer built with
+scale=False or shift=False) and mixed stacks run as torch ops, layer by layer,
+and so does Flow.backward of an affine flow under autograd (the native inverse
+has no reverse mode).  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops
+as well, CNF_RADIAL_NATIVE=0 radial ones and CNF_AFFINE_NATIVE=0 affine ones.  A radial stack's log-det is the reference's
 constant log(1) = 0: the native path returns the same 0-d fp32 zero.
 
-A planar or radial stack's other launches hang off the same kind of binding
-(cnf_hip/planar.py, cnf_hip/radial.py over the base both share,
+A planar, radial or affine stack's other launches hang off the same kind of
+binding (cnf_hip/planar.py, cnf_hip/radial.py, cnf_hip/affine.py over the base
+they share,
 cnf_hip/rowstack.py): the fused training step and loss
 evaluation, the calibrator's fused predict and score (cnf_planar_predict,
-cnf_radial_predict, ..._score) and the one-launch Adam step
+cnf_radial_predict, cnf_affine_predict, ..._score) and the one-launch Adam step
 (cnf_adam_step_tensors); calibrators.TorchFlowCalibrator drives them, HIP-graph
 epoch replay included.
 """
@@ -55,6 +59,9 @@ PLANAR_NATIVE = os.environ.get("CNF_PLANAR_NATIVE", "1") != "0"
 # CNF_RADIAL_NATIVE=0: the same for radial flows (the baseline of
 # tools/radial_bench.py).
 RADIAL_NATIVE = os.environ.get("CNF_RADIAL_NATIVE", "1") != "0"
+# CNF_AFFINE_NATIVE=0: the same for affine-constant flows (the baseline of
+# tools/affine_bench.py).
+AFFINE_NATIVE = os.environ.get("CNF_AFFINE_NATIVE", "1") != "0"
 
 _warned = set()
 
@@ -99,12 +106,13 @@ def _native_eligible(layers, x):
 
 
 def _row_class(layers, x):
-    """The stack class (PlanarStack / RadialStack) under which these layers can
+    """The stack class (PlanarStack / RadialStack / AffineStack) under which these layers can
     run on x as one fused launch of a row-wise family, or None.  The family's
     switch is read here, at call time, and with the input's device before
     anything of cnf_hip is touched."""
     family = getattr(layers[0], "_family", None) if layers else None
-    if family is None or not (PLANAR_NATIVE if family == "planar" else RADIAL_NATIVE):
+    if family is None or not {"planar": PLANAR_NATIVE, "radial": RADIAL_NATIVE,
+                              "affine": AFFINE_NATIVE}[family]:
         return None
     if not _device_rows(x):
         return None
@@ -121,8 +129,10 @@ def _row_class(layers, x):
 def _run_stack(stack, x, want_all, inverse=False):
     """(zs list | final z, log-det) from one fused launch of any stack (a
     RadialStack's log-det is the 0-d zero), under autograd when a gradient is
-    wanted, or None when the shape is outside the kernels' envelope.  Only a
-    CouplingStack has an inverse."""
+    wanted, or None when the shape is outside the kernels' envelope.  A
+    CouplingStack and an AffineStack have an inverse; only the former's has a
+    reverse mode.  An AffineStack's log-det keeps its shape [1], as the
+    reference's torch.sum(s, dim=1) does for every batch size."""
     from cnf_hip._lib import UnsupportedShape
     try:
         if torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad()):
@@ -136,22 +146,32 @@ def _run_stack(stack, x, want_all, inverse=False):
             else:
                 fin, ld, allt = stack.run(x, want_all=want_all)
             out = allt if want_all else fin
-        return (list(out.unbind(0)) if want_all else out), _squeeze_ld(ld)
+        if stack.squeeze_logdet:
+            ld = _squeeze_ld(ld)
+        return (list(out.unbind(0)) if want_all else out), ld
     except UnsupportedShape as e:
         _not_native(str(e))
         return None
 
 
-def _layer_native(layer, x):
-    """A PlanarLayer's or RadialLayer's forward as one fused launch on its own
-    single-layer stack (rebuilt when a parameter was replaced), or None."""
+def _wants_grad(x, stack):
+    return torch.is_grad_enabled() and (x.requires_grad or stack.requires_grad())
+
+
+def _layer_native(layer, x, inverse=False):
+    """A PlanarLayer's, RadialLayer's or AffineConstantLayer's forward (the
+    last one's inverse as well, when no gradient is wanted) as one fused launch
+    on its own single-layer stack (rebuilt when a parameter was replaced), or
+    None."""
     cls = _row_class([layer], x)
-    if cls is None:
+    if cls is None or (inverse and not cls.has_inverse):
         return None
     st = getattr(layer, "_stack", None)
     if st is None or any(t is not p for t, p in zip(st.param_tensors(), cls.layer_tensors(layer))):
         st = layer._stack = cls([layer])
-    return _run_stack(st, x, want_all=False)
+    if inverse and _wants_grad(x, st):
+        return None
+    return _run_stack(st, x, False, inverse)
 
 
 def _squeeze_ld(ld):
@@ -174,8 +194,8 @@ class Flow(nn.Module):
         self._drop_bindings(self.__dict__)
 
     # the lazily built native bindings, each with the key it was built for:
-    # the CouplingStack, the PlanarStack, the RadialStack
-    _BINDINGS = ("_stack", "_pstack", "_rstack")
+    # the CouplingStack, the PlanarStack, the RadialStack, the AffineStack
+    _BINDINGS = ("_stack", "_pstack", "_rstack", "_astack")
 
     @classmethod
     def _drop_bindings(cls, attrs):
@@ -201,7 +221,7 @@ class Flow(nn.Module):
 
     def _row_stack(self, cls, layers):
         """The stack of class `cls` over `layers` (list(self.layers)), kept in
-        the slot the class names (_pstack, _rstack) and rebuilt when a layer or
+        the slot the class names (_pstack, _rstack, _astack) and rebuilt when a layer or
         one of its parameters was replaced; a flow unpickled from before the
         slot existed builds it as well."""
         tensors = cls.layer_tensors
@@ -236,9 +256,16 @@ class Flow(nn.Module):
     def _try_native(self, x, inverse, want_all=True):
         """(zs list | final z, log-det) from one fused launch, or None."""
         layers = list(self.layers)
-        cls = None if inverse else _row_class(layers, x)
+        cls = _row_class(layers, x)
         if cls is not None:
-            return _run_stack(self._row_stack(cls, layers), x, want_all)
+            if not inverse:
+                return _run_stack(self._row_stack(cls, layers), x, want_all)
+            if not cls.has_inverse:
+                return None
+            # a row family's inverse (affine) has no reverse mode: under
+            # autograd it stays on the torch ops
+            st = self._row_stack(cls, layers)
+            return None if _wants_grad(x, st) else _run_stack(st, x, want_all, True)
         if not _native_eligible(layers, x):
             return None
         return _run_stack(self._native_stack(), x, want_all, inverse)
@@ -292,13 +319,23 @@ class Flow(nn.Module):
 
 class AffineConstantLayer(nn.Module):
     """z = x*exp(s) + t with per-feature constants (reference flows/flows.py:40-65).
-    Not a coupling layer: torch ops on every device."""
+    With both parameters, on a ROCm device one fused launch per direction
+    (cnf_affine_forward / cnf_affine_inverse, L = 1; the inverse only when no
+    gradient is wanted); torch ops on the host and for scale=False /
+    shift=False layers.  The log-det has shape [1]."""
+    _family = "affine"
 
     def __init__(self, dim, scale=True, shift=True):
         super().__init__()
         self.s = nn.Parameter(torch.zeros(1, dim, requires_grad=True)) if scale else None
         self.t = nn.Parameter(torch.zeros(1, dim, requires_grad=True)) if shift else None
         self.invertible = True
+        self._stack = None
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_stack"] = None
+        return st
 
     def _st(self, x):
         s = self.s if self.s is not None else x.new_zeros(x.size())
@@ -306,10 +343,16 @@ class AffineConstantLayer(nn.Module):
         return s, t
 
     def forward(self, x):
+        out = _layer_native(self, x)
+        if out is not None:
+            return out
         s, t = self._st(x)
         return x * torch.exp(s) + t, torch.sum(s, dim=1)
 
     def backward(self, z):
+        out = _layer_native(self, z, inverse=True)
+        if out is not None:
+            return out
         s, t = self._st(z)
         return (z - t) * torch.exp(-s), torch.sum(-s, dim=1)
 

@@ -567,6 +567,107 @@ int cnf_radial_loss_vjp(int32_t dim, int32_t n_layers, const float* const* param
                         float* loss_terms, float* grads, float* dx, int64_t B, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Affine-constant flows: a Flow of the reference's AffineConstantLayers
+ * (flows/flows.py:40-65; train-flows-det.ipynb, AffineConstantFlow), each with
+ * both parameters s [1][D], t [1][D] (that state_dict order):
+ *   forward  z = x * exp(s) + t,    log_det = sum_d s     (one number, not per row)
+ *   inverse  x = (z - t) * exp(-s), log_det = sum_d -s
+ * A layer rounds as torch's ops do (product, then sum; difference, then
+ * product) and the layers are applied one after another, never composed.  The
+ * stack's log-det is an fp32 sum over d per layer, then 0 + ld_0 + ld_1 + ...
+ * in the direction's layer order, formed once per call: logdet / gld below are
+ * [1] DEVICE floats and may be NULL.  All fp32.
+ *   dim       D, 1..CNF_MAX_DIM;  n_layers  L, 1..CNF_AFFINE_MAX_LAYERS
+ *             (< 1: CNF_ERR_DESC; above: CNF_ERR_UNSUPPORTED)
+ *   params    HOST array of 2 * L DEVICE pointers: s, t of layer 0, 1, ...
+ *             (non-NULL, 4-byte aligned)
+ *   B         0..2^31 rows (CNF_ERR_BATCH otherwise)
+ *   workspace cnf_affine_workspace_bytes(dim, n_layers, B) bytes of DEVICE
+ *             memory, no initialisation needed; one size serves every entry
+ *             point.  A call first writes each layer's (exp(+-s), t, log-det)
+ *             there with one small launch, so nothing is cached between calls.
+ * In floats, with LPR, DP, r64, F and U as for the planar family and
+ * PW = L * 2 D + 4, the workspace holds
+ *   r64(L * (2 DP + 8)) + r64(PW) + r64(max(U * PW, 4 * F))
+ * There is no per-row tape: the reverse mode keeps each layer's input in
+ * registers up to 10 layers, and above keeps every 16th and runs the row
+ * forward from it (a layer's input is never rebuilt by inverting the layer).
+ * Argument errors, the B == 0 rule (memset nodes only), determinism and the
+ * absence of atomics, allocation and host synchronisation are the planar
+ * family's.  A deliberate limit of B == 0: the log-det does not depend on the
+ * rows, but no kernel runs to form it, so logdet is ZEROED (not sum_d s) and
+ * cnf_affine_vjp zeroes grads without adding gld to the s entries; a caller
+ * that needs either for an empty batch forms it itself (cnf_hip/affine.py
+ * does, with torch ops). */
+#define CNF_AFFINE_MAX_LAYERS 64
+
+/* 2 * L tensors, 2 * L * D floats. */
+int cnf_affine_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats);
+int cnf_affine_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B, size_t* bytes);
+/* As cnf_planar_launch_plan; regt: every layer's input in registers (L <= 10);
+ * rega: LPR == 1 and D <= 10 at L <= 10. */
+int cnf_affine_launch_plan(int32_t dim, int32_t n_layers, int64_t B, int32_t out[8]);
+
+/* Flow.forward of the stack: z [B][D] (= zs[-1]), logdet [1], z_all [L][B][D]
+ * (the zs list); each may be NULL. */
+int cnf_affine_forward(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, float* z, float* logdet, float* z_all, int64_t B,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Flow.backward of the stack (the INVERSE transform): x [B][D] (= xs[-1]),
+ * logdet [1] (the sum of -sum_d s from the last layer to the first), x_all
+ * [L][B][D] with x_all[k] the rows after undoing layer L-1-k (the xs list);
+ * each may be NULL.  There is no reverse mode of the inverse. */
+int cnf_affine_inverse(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* z, float* x, float* logdet, float* x_all, int64_t B,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Forward + loss terms, as cnf_planar_forward_loss: the per-row loss is
+ * -(log(softmax(z)[y] + 1e-7) + ld) for CNF_LOSS_CAL and ce - det * ld for
+ * CNF_LOSS_CE; loss_terms[3] = {sum of per-row loss, sum of ce, B * ld}; z and
+ * logdet [1] may be NULL.  A label outside [0, D) makes the terms NaN. */
+int cnf_affine_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
+                            const float* x, const int64_t* y, int32_t loss_kind, float det,
+                            float* z, float* logdet, float* loss_terms, int64_t B,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Calibrator.predict of an affine flow calibrator, per row:
+ *   xc = x - mean(x);  z = affine stack(xc);  p = softmax(z)
+ *   probs = softmax(log(p + 1e-7) - log_priors)
+ * in one pass that keeps the row in registers.  log_priors [D] DEVICE floats;
+ * probs [B][D].  Envelope, workspace, prepare launch, validation, B == 0 rule
+ * and determinism as cnf_affine_forward. */
+int cnf_affine_predict(int32_t dim, int32_t n_layers, const float* const* params,
+                       const float* x, const float* log_priors, float* probs, int64_t B,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* The score variant of cnf_affine_predict, as cnf_planar_score is of
+ * cnf_planar_predict: ONE launch that ADDS into `record` the words that
+ * cnf_affine_predict followed by cnf_metrics(probs, y, ...) would leave; the
+ * probabilities are never stored.  Validation is the sibling's plus
+ * cnf_metrics' (2 <= dim, bins in 1..CNF_MAX_BINS, B <= 2^26, y and record
+ * 8-byte aligned, record non-NULL), all before any HIP call.  B == 0 returns
+ * CNF_OK without a launch and leaves the record as it is. */
+int cnf_affine_score(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                     const float* log_priors, const int64_t* y, int32_t bins, int64_t* record,
+                     int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Reverse mode of cnf_affine_forward: upstream gz [B][D], gz_all [L][B][D],
+ * gld [1] (each may be NULL = zero); writes grads [cnf_affine_param_count]
+ * (per layer s, t; overwritten) and dx [B][D] (may be NULL).  With G_l the
+ * gradient at layer l's output: grad t_l = sum_rows G_l, grad s_l = sum_rows
+ * G_l z_{l-1} exp(s_l) + gld, G_{l-1} = G_l exp(s_l). */
+int cnf_affine_vjp(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
+                   const float* gz, const float* gz_all, const float* gld, float* grads,
+                   float* dx, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fused forward + loss + reverse mode, as cnf_planar_loss_vjp: loss_terms[3]
+ * (sums over this batch), grads = grad_scale * d(sum of the per-row loss)/
+ * d(params), dx [B][D] likewise, may be NULL. */
+int cnf_affine_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
+                        const float* x, const int64_t* y, int32_t loss_kind, float det,
+                        float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"
