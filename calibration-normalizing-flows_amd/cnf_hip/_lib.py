@@ -35,6 +35,16 @@ PLANAR_REG_LAYERS = 10  # deeper stacks keep their tanh tape in the workspace
 RADIAL_MAX_LAYERS = 64  # CNF_RADIAL_MAX_LAYERS (cnf_radial_*)
 RADIAL_REG_LAYERS = 10  # deeper stacks keep their tape of r in the workspace
 AFFINE_MAX_LAYERS = 64  # CNF_AFFINE_MAX_LAYERS (cnf_affine_*)
+VJP_PLAN_WORDS = 16     # CNF_VJP_PLAN_WORDS (cnf_vjp_launch_plan)
+VJP_PATHS = ("none", "vjp2", "vjp-rows", "layerwise", "wide-fused")  # CNF_VJP_PATH_*
+# k_wgemm's instantiations in cnf_vjp_launch_plan's bit order: (BT, EPI, PAIR, NC)
+WGEMM_BITS = tuple((bt, epi, pair, nc)
+                   for bt, epi, pair in ((True, "bias", False), (True, "bias_relu", False),
+                                         (False, "mask", False), (False, "add", True),
+                                         (False, "add", False))
+                   for nc in (1, 2))
+# k_wdw16g's (G tiles, H tiles) classes in its bit order (CNF_DWG_CLASSES, cnf_wvjp.hip)
+WDWG_CLASSES = ((7, 4), (7, 7), (4, 7), (4, 4), (4, 2), (4, 5), (1, 5))
 
 # Every symbol include/cnf.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -59,7 +69,7 @@ EXPORTS = (
     "cnf_affine_forward", "cnf_affine_inverse",
     "cnf_affine_forward_loss", "cnf_affine_predict", "cnf_affine_score", "cnf_affine_vjp",
     "cnf_affine_loss_vjp",
-    "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
+    "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_vjp_launch_plan", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
 
@@ -191,6 +201,7 @@ def _bind(lib):
                                                P, I64, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_vjp_kernel_name": (ctypes.c_char_p, [D]),
+        "cnf_vjp_launch_plan": (ctypes.c_int, [D, I64, I32, ctypes.POINTER(I32)]),
         "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
         "cnf_last_hip_error": (ctypes.c_int, []),
         "cnf_abi_version": (ctypes.c_int, []),

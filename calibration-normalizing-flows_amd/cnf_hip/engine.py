@@ -32,6 +32,27 @@ def _ops():
     return _lib.torch_ops() if USE_TORCH_OPS else None
 
 
+def vjp_launch_plan(desc, B, inverse=False):
+    """cnf_vjp_launch_plan (host only) as a dict with "path" and, per path, the
+    fields include/cnf.h lists -- layerwise: kNJ, keep_acts, nkb, rows_kb,
+    nseed, wave_blocks, dw16_z, gemms (a set of (BT, EPI, PAIR, NC)), ny,
+    chunks; wide-fused: row, nets, nkb, rows_kb, nseed, wdwg, dw16_z, classes
+    (a set of (G tiles, H tiles))."""
+    out = (ctypes.c_int32 * _lib.VJP_PLAN_WORDS)()
+    _lib.check("cnf_vjp_launch_plan", _lib.lib().cnf_vjp_launch_plan(
+        ctypes.byref(desc), ctypes.c_int64(B), ctypes.c_int32(int(bool(inverse))), out))
+    plan = {"path": _lib.VJP_PATHS[out[0]]}
+    bits = lambda names, w: {n for i, n in enumerate(names) if w >> i & 1}
+    if plan["path"] == "layerwise":
+        plan.update(kNJ=out[1], keep_acts=bool(out[2]), nkb=out[3], rows_kb=out[4],
+                    nseed=out[5], wave_blocks=out[6], dw16_z=out[7],
+                    gemms=bits(_lib.WGEMM_BITS, out[8]), ny=out[9], chunks=out[10])
+    elif plan["path"] == "wide-fused":
+        plan.update(row=out[1], nets=out[2], nkb=out[3], rows_kb=out[4], nseed=out[5],
+                    wdwg=bool(out[6]), dw16_z=out[7], classes=bits(_lib.WDWG_CLASSES, out[8]))
+    return plan
+
+
 class CouplingStack(Stack):
     """A fused stack of NvpCouplingLayers (flows/flows.py:68-126) sharing
     dim / hidden_size / scale / shift.  Layers keep owning their parameters;
@@ -114,6 +135,11 @@ class CouplingStack(Stack):
         """Reverse-mode path of cnf_vjp / cnf_loss_vjp for this stack: "vjp2",
         "vjp-rows", "layerwise", "wide-fused" or "none" (cnf_vjp_kernel_name)."""
         return _lib.lib().cnf_vjp_kernel_name(ctypes.byref(self.desc)).decode()
+
+    def vjp_launch_plan(self, B, inverse=False):
+        """What the reverse mode of a call on B rows launches (vjp_launch_plan
+        above; inverse: cnf_vjp_inverse)."""
+        return vjp_launch_plan(self.desc, B, inverse)
 
     def has_native_vjp(self):
         """True when cnf_vjp serves this descriptor (every shape within the

@@ -357,4 +357,16 @@ const char* cnf_vjp_kernel_name(const cnf_desc* desc) {
   return vjp_path_name(s);
 }
 
+int cnf_vjp_launch_plan(const cnf_desc* desc, int64_t B, int32_t inverse,
+                        int32_t out[CNF_VJP_PLAN_WORDS]) {
+  Shape s;
+  int st = derive_shape(desc, &s);
+  if (st != CNF_OK) return st;
+  if (!out) return CNF_ERR_NULL;
+  if (B < 0) return CNF_ERR_BATCH;
+  if (inverse != 0 && inverse != 1) return CNF_ERR_DESC;
+  vjp_launch_plan(s, B, inverse != 0, out);
+  return CNF_OK;
+}
+
 }  // extern "C"

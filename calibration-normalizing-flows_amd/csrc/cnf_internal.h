@@ -180,6 +180,7 @@ struct WTrain16Layout {
 // 32 w + 16 g + i, column c at w * 32 W + (c >> 4) * 512 + g * 256 + i * 16 +
 // (c & 15)); one array of a layer is wide16_blocks(B) * 32 * W floats.
 int wide16_train_layout(const Shape& s, WTrain16Layout* out);
+int wide16_table_row(const Shape& s);  // the shape's row of kW16Table, -1: none
 inline int64_t wide16_blocks(int64_t B) { return (B + 31) / 32; }
 // The loss seed fused into the forward sweep (null: the final output goes to
 // zst / ld for k_wseed): per row the gradient of z_L (G, [B][D]) and of ld
@@ -208,6 +209,8 @@ bool wvjp_ok(const Shape& s);
 bool wvjp_fused16(const Shape& s);  // ... through the fused wide sweeps (at B = 1)
 int wvjp_workspace(const Shape& s, int64_t B, size_t* bytes);
 int wvjp_inv_workspace(const Shape& s, int64_t B, size_t* bytes);
+// cnf_vjp_launch_plan's words for the layerwise / wide-fused paths (out zeroed by the caller)
+void wvjp_launch_plan(const Shape& s, int64_t B, bool inverse, int32_t* out);
 int wvjp_run(const Shape& s, const void* prepared, const float* x, const int64_t* y,
              const float* gz, const float* gz_all, const float* gld, int kind, float det,
              float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B, void* ws,
@@ -221,6 +224,8 @@ int wvjp_inv_run(const Shape& s, const void* prepared, const float* z, const flo
 int vjp_workspace(const Shape& s, int64_t B, size_t* bytes);
 // "vjp2", "vjp-rows", "layerwise", "wide-fused" or "none" (cnf_vjp_kernel_name)
 const char* vjp_path_name(const Shape& s);
+// cnf_vjp_launch_plan: out[CNF_VJP_PLAN_WORDS] for the path a call on B rows takes
+void vjp_launch_plan(const Shape& s, int64_t B, bool inverse, int32_t* out);
 bool vjp2_ok(const Shape& s);  // the packed-pair SGPR reverse-mode kernel serves this shape
 // kind < 0: generic VJP from gz / gz_all / gld;  kind = CNF_LOSS_*: fused loss
 int vjp_run(const Shape& s, const void* prepared, const float* x, const int64_t* y,

@@ -662,6 +662,18 @@ const char* vjp_path_name(const Shape& s) {
   return "none";
 }
 
+void vjp_launch_plan(const Shape& s, int64_t B, bool inverse, int32_t* out) {
+  for (int i = 0; i < CNF_VJP_PLAN_WORDS; ++i) out[i] = 0;
+  // the inverse's reverse mode runs layer at a time for every shape (wvjp_inv_run)
+  const VjpPath path = inverse ? VjpPath::kLayerwise : vjp_path(s);
+  switch (path) {
+    case VjpPath::kV2: out[0] = CNF_VJP_PATH_VJP2; return;
+    case VjpPath::kRows: out[0] = CNF_VJP_PATH_ROWS; return;
+    case VjpPath::kLayerwise: wvjp_launch_plan(s, B, inverse, out); return;
+    case VjpPath::kNone: return;
+  }
+}
+
 // workspace of k_vjp2: [per-wave partials][x_T stash], the stash 256-B aligned
 size_t v2_stash_offset(const Shape& s, int64_t nblk) {
   return ((size_t)(nblk > 0 ? nblk : 1) * partial_stride(s) * 4 + 255) / 256 * 256;

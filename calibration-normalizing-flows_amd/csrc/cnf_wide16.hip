@@ -1305,6 +1305,12 @@ static int64_t w16_lt(const WEntry16* e, int nets) {
   return (int64_t)pad_bwd(ls) * 64;
 }
 
+// the shape's row of kW16Table, -1: none (cnf_vjp_launch_plan)
+int wide16_table_row(const Shape& s) {
+  const WEntry16* e = w16find(s);
+  return e ? (int)(e - kW16Table) : -1;
+}
+
 int64_t wide_layer_floats(const Shape& s) {
   const WEntry16* e = w16find(s);
   return e ? w16_la(e, s.nets) + (int64_t)s.nets * e->nb + w16_lt(e, s.nets) : 0;

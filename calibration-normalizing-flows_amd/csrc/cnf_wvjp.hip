@@ -624,12 +624,17 @@ __device__ __forceinline__ void wdwg_rr(const DwJob& j, const DwArgs& da, float*
 // the (G tiles, H tiles) classes with an instantiation: the weight gradients
 // of k_wide16's table (cfg4: (7, 4), (7, 7), (4, 7))
 #define CNF_DWG_CLASSES(X) X(7, 4) X(7, 7) X(4, 7) X(4, 4) X(4, 2) X(4, 5) X(1, 5)
-inline bool wdwg_class_ok(int ntg, int nth) {
-#define CNF_DWG_OK(A, B) if (ntg == A && nth == B) return true;
-  CNF_DWG_CLASSES(CNF_DWG_OK)
-#undef CNF_DWG_OK
-  return false;
+// a job's class: its position in CNF_DWG_CLASSES, or -1 (no instantiation)
+inline int wdwg_class(int ntg, int nth) {
+  int at = 0;
+#define CNF_DWG_AT(A, B)                 \
+  if (ntg == A && nth == B) return at; \
+  ++at;
+  CNF_DWG_CLASSES(CNF_DWG_AT)
+#undef CNF_DWG_AT
+  return -1;
 }
+inline bool wdwg_class_ok(int ntg, int nth) { return wdwg_class(ntg, nth) >= 0; }
 
 __global__ __launch_bounds__(256, 2) void k_wdw16g(DwArgs da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1211,25 +1216,49 @@ size_t gemm_lds(int cols, int K, bool pair) {
   return (size_t)((K + 7) & ~7) * (32 * gemm_nc(cols) + 8) * 4 * (pair ? 2 : 1);
 }
 
+int gemm_ny(int cols) { return (cols + kBN - 1) / kBN; }  // column blocks (grid)
+
+// reduction chunks of k_wgemm's loop over [0, r8(K)) in steps of kKC
+int gemm_chunks(int K) { return (r8(K) + kKC - 1) / kKC; }
+
+// The five (BT, EPI, PAIR) forms k_wgemm is instantiated in, as launch_nc
+// picks them; with NC the instantiation's bit in cnf_vjp_launch_plan's set
+// is 2 * form + (NC - 1).
+enum GemmForm { kFormBias = 0, kFormBiasRelu, kFormMask, kFormAddPair, kFormAdd };
+int gemm_form(bool bt, int epi, bool pair) {
+  if (bt && epi == kEpiBias) return kFormBias;
+  if (bt && epi == kEpiBiasRelu) return kFormBiasRelu;
+  if (!bt && epi == kEpiMask) return kFormMask;
+  if (!bt && epi == kEpiAdd && pair) return kFormAddPair;
+  return kFormAdd;
+}
+
 template <int NC>
 void launch_nc(bool bt, int epi, bool pair, dim3 grid, size_t lds, hipStream_t st,
                const GemmArgs& ga) {
-  if (bt && epi == kEpiBias)
-    hipLaunchKernelGGL((k_wgemm<true, kEpiBias, false, NC>), grid, dim3(256), lds, st, ga);
-  else if (bt && epi == kEpiBiasRelu)
-    hipLaunchKernelGGL((k_wgemm<true, kEpiBiasRelu, false, NC>), grid, dim3(256), lds, st, ga);
-  else if (!bt && epi == kEpiMask)
-    hipLaunchKernelGGL((k_wgemm<false, kEpiMask, false, NC>), grid, dim3(256), lds, st, ga);
-  else if (!bt && epi == kEpiAdd && pair)
-    hipLaunchKernelGGL((k_wgemm<false, kEpiAdd, true, NC>), grid, dim3(256), lds, st, ga);
-  else
-    hipLaunchKernelGGL((k_wgemm<false, kEpiAdd, false, NC>), grid, dim3(256), lds, st, ga);
+  switch (gemm_form(bt, epi, pair)) {
+    case kFormBias:
+      hipLaunchKernelGGL((k_wgemm<true, kEpiBias, false, NC>), grid, dim3(256), lds, st, ga);
+      break;
+    case kFormBiasRelu:
+      hipLaunchKernelGGL((k_wgemm<true, kEpiBiasRelu, false, NC>), grid, dim3(256), lds, st, ga);
+      break;
+    case kFormMask:
+      hipLaunchKernelGGL((k_wgemm<false, kEpiMask, false, NC>), grid, dim3(256), lds, st, ga);
+      break;
+    case kFormAddPair:
+      hipLaunchKernelGGL((k_wgemm<false, kEpiAdd, true, NC>), grid, dim3(256), lds, st, ga);
+      break;
+    default:
+      hipLaunchKernelGGL((k_wgemm<false, kEpiAdd, false, NC>), grid, dim3(256), lds, st, ga);
+      break;
+  }
 }
 
 // One GEMM launch over B rows; cols = columns written (N plus pad).
 void gemm(GemmArgs ga, int64_t B, int cols, int K, int nz, bool bt, int epi, bool pair,
           hipStream_t st) {
-  const unsigned ny = (unsigned)((cols + kBN - 1) / kBN);
+  const unsigned ny = (unsigned)gemm_ny(cols);
   const size_t lds = gemm_lds(cols, K, pair);
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, 160 * 1024 / lds));
   const int64_t want = std::max<int64_t>(1, (int64_t)256 * per_cu / (ny * nz));
@@ -1241,6 +1270,46 @@ void gemm(GemmArgs ga, int64_t B, int cols, int K, int nz, bool bt, int epi, boo
     case 2: launch_nc<2>(bt, epi, pair, grid, lds, st, ga); break;
     default: launch_nc<2>(bt, epi, pair, grid, lds, st, ga); break;
   }
+}
+
+// What one GEMM launch of a layer's sweep is, apart from its operands: the
+// arguments Runner passes to gemm(), and what cnf_vjp_launch_plan reports.
+struct GemmCall {
+  int cols, K, nz;
+  bool bt;
+  int epi;
+  bool pair;
+};
+// Linear k of the conditioners, forward (nets_forward)
+GemmCall fwd_call(const Shape& s, int k) {
+  const bool last = k == s.n_lin - 1;
+  return {last ? lin_out(s, k) : hp(s, k), lin_in(s, k), s.nets, true,
+          last ? kEpiBias : kEpiBiasRelu, false};
+}
+// back through Linear k >= 1 into hidden k - 1 (nets_backward)
+GemmCall bwd_call(const Shape& s, int k) {
+  return {gp(s, k - 1), lin_out(s, k), s.nets, false, kEpiMask, false};
+}
+// back through the first Linear of both nets into the layer's input gradient
+GemmCall bwd_first_call(const Shape& s) {
+  return {s.strict ? s.D : s.DC, lin_out(s, 0), 1, false, kEpiAdd, s.nets == 2};
+}
+
+// rows of the update / stash / scatter kernels' grids (one wave per row, four
+// per block; grid-stride past the cap)
+unsigned wave_grid(int64_t B) { return (unsigned)std::min<int64_t>((B + 3) / 4, 16384); }
+
+// k_wdw16's grid z over a layer's jobs: 128-row groups x column groups of
+// kDw16CT 16-column tiles of [H | 1]
+int dw16_subs(int N, int K) {
+  const int ncg = ((K + 1 + 15) / 16 + kDw16CT - 1) / kDw16CT;
+  return ((N + 127) / 128) * ncg;
+}
+// ... of the layer-at-a-time sweeps, whose job k is lin_out(k) x (lin_in(k) + 1)
+int layer_dw16_subs(const Shape& s) {
+  int m = 1;
+  for (int k = 0; k < s.n_lin; ++k) m = std::max(m, dw16_subs(lin_out(s, k), lin_in(s, k)));
+  return m;
 }
 
 }  // namespace
@@ -1313,6 +1382,37 @@ bool plan16(const Shape& s, int64_t B, WTrain16Layout* lay, Plan16* p) {
   return true;
 }
 
+// Linear k's weight-gradient job of the fused sweeps: the last G / H column of
+// its parts in the wave-tiled arrays (slot order) and its dW's rows and columns
+struct Dw16Job {
+  int gcl, hcl, N, K;
+};
+Dw16Job dw16_job(const Shape& s, const WTrain16Layout& lay, int k) {
+  const bool last = k == s.n_lin - 1;
+  return {(last ? lay.ts : lay.gpw[k + 1]) - 1, (k == 0 ? lay.cw : lay.hw[k]) - 1,
+          last ? s.DT : s.units[k + 1], k == 0 ? s.DC : s.units[k]};
+}
+// Which kernel takes a layer's weight gradients: k_wdw16g when every job is in
+// one of its classes (their set as bits in CNF_DWG_CLASSES order; maxtpc sizes
+// its LDS stages), else k_wdw16 with max_subs as its grid z.
+struct Dw16Pick {
+  bool gok;
+  int maxtpc, max_subs;
+  unsigned classes;
+};
+Dw16Pick dw16_pick(const Shape& s, const WTrain16Layout& lay) {
+  Dw16Pick p{true, 0, 1, 0u};
+  for (int k = 0; k < s.n_lin; ++k) {  // both nets' jobs have one shape
+    const Dw16Job j = dw16_job(s, lay, k);
+    const int ng = (j.gcl >> 4) + 1, nh = (j.hcl >> 4) + 1, c = wdwg_class(ng, nh);
+    p.gok = p.gok && c >= 0;
+    if (c >= 0) p.classes |= 1u << c;
+    p.maxtpc = std::max(p.maxtpc, ng + nh);
+    p.max_subs = std::max(p.max_subs, dw16_subs(j.N, j.K));
+  }
+  return p;
+}
+
 int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const void* prepared,
                const float* x, const int64_t* y, const float* gz, const float* gz_all,
                const float* gld_in, int kind, float det, float grad_scale, float* loss_terms,
@@ -1353,21 +1453,22 @@ int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const
     da.M = B;
     da.rows = p.rows_kb;
     da.PS = PS;
-    int jobs = 0, max_subs = 1;
+    int jobs = 0;
     for (int n = 0; n < s.nets; ++n)
       for (int k = 0; k < NL; ++k) {
         DwJob& j = da.job[jobs++];
         const bool last = k == NL - 1;
+        const Dw16Job js = dw16_job(s, lay, k);
         // wave-tiled parts: a part starting at column c begins (c / 16) * 512
         // floats into each 32-row block
         j.G = gl + (int64_t)(last ? lay.glast[n] : lay.gpre[n][k + 1]) / 16 * 512;
         j.ldg = lay.GW;
-        j.gcl = (last ? lay.ts : lay.gpw[k + 1]) - 1;
+        j.gcl = js.gcl;
         j.H = tl + (int64_t)(k == 0 ? lay.xc : lay.h[n][k]) / 16 * 512;
         j.ldh = lay.RW;
-        j.hcl = (k == 0 ? lay.cw : lay.hw[k]) - 1;
-        j.N = last ? s.DT : s.units[k + 1];
-        j.K = k == 0 ? s.DC : s.units[k];
+        j.hcl = js.hcl;
+        j.N = js.N;
+        j.K = js.K;
         j.slot = 1;
         j.cstep = 1;
         j.rrev = 0;
@@ -1376,22 +1477,15 @@ int wvjp16_run(const Shape& s, const WTrain16Layout& lay, const Plan16& p, const
         j.wld = s.units[k];
         j.boff = n * s.net_floats + lin_off(s, k) + (int64_t)s.units[k + 1] * s.units[k];
         j.tiles_c = (j.K + 1 + 31) / 32;
-        const int ncg = ((j.K + 1 + 15) / 16 + kDw16CT - 1) / kDw16CT;
-        max_subs = std::max(max_subs, ((j.N + 127) / 128) * ncg);
       }
-    int maxtpc = 0;
-    bool gok = true;  // every job in a k_wdw16g class, else k_wdw16
-    for (int q = 0; q < jobs; ++q) {
-      const int ng = (da.job[q].gcl >> 4) + 1, nh = (da.job[q].hcl >> 4) + 1;
-      gok = gok && wdwg_class_ok(ng, nh);
-      maxtpc = std::max(maxtpc, ng + nh);
-    }
-    if (gok) {  // whole 32-row blocks (padding rows carry zero G)
+    const Dw16Pick pick = dw16_pick(s, lay);
+    if (pick.gok) {  // whole 32-row blocks (padding rows carry zero G)
       da.M = Bp;
       hipLaunchKernelGGL(k_wdw16g, dim3((unsigned)p.nkb, (unsigned)jobs), dim3(256),
-                         (size_t)2 * maxtpc * 2048, st, da);
+                         (size_t)2 * pick.maxtpc * 2048, st, da);
     } else {
-      hipLaunchKernelGGL(k_wdw16, dim3((unsigned)p.nkb, (unsigned)jobs, (unsigned)max_subs),
+      hipLaunchKernelGGL(k_wdw16,
+                         dim3((unsigned)p.nkb, (unsigned)jobs, (unsigned)pick.max_subs),
                          dim3(256), 0, st, da);
     }
     reduce_partials(part, (int)p.nkb, (int)PS, (int)PL, grads + (int64_t)l * PL, nullptr, st);
@@ -1414,6 +1508,47 @@ bool wvjp_fused16(const Shape& s) {
   WTrain16Layout lay;
   Plan16 p16;
   return wvjp_ok(s) && plan16(s, 1, &lay, &p16);
+}
+
+// cnf_vjp_launch_plan for the MFMA family (the words: include/cnf.h), every
+// field from the helper the launches above and below call.  Host only.
+void wvjp_launch_plan(const Shape& s, int64_t B, bool inverse, int32_t* out) {
+  auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, 0x7fffffff); };
+  if (!wvjp_ok(s)) return;  // out[0] stays CNF_VJP_PATH_NONE
+  const int64_t Bn = B > 0 ? B : 1;
+  WTrain16Layout lay;
+  Plan16 p16;
+  if (!inverse && plan16(s, Bn, &lay, &p16)) {
+    const Dw16Pick pick = dw16_pick(s, lay);
+    out[0] = CNF_VJP_PATH_WIDE_FUSED;
+    out[1] = wide16_table_row(s);
+    out[2] = s.nets;
+    out[3] = i32(p16.nkb);
+    out[4] = i32(p16.rows_kb);
+    out[5] = i32(p16.nseed);
+    out[6] = pick.gok ? 1 : 0;
+    out[7] = pick.gok ? 0 : pick.max_subs;
+    out[8] = (int32_t)pick.classes;
+    return;
+  }
+  const Plan p = make_plan(s, Bn);
+  out[0] = CNF_VJP_PATH_LAYERWISE;
+  out[1] = inverse ? 0 : pick_nj(s.D, 1, 2, 3, 4);
+  out[2] = p.keep_acts ? 1 : 0;
+  out[3] = i32(p.nkb);
+  out[4] = i32(p.rows_kb);
+  out[5] = i32(p.nseed);
+  out[6] = (int32_t)wave_grid(Bn);
+  if (!s.nets) return;  // no conditioner: no GEMM, no weight gradients
+  out[7] = layer_dw16_subs(s);
+  auto add = [&](const GemmCall& c) {
+    out[8] |= 1 << (2 * gemm_form(c.bt, c.epi, c.pair) + gemm_nc(c.cols) - 1);
+    out[9] = std::max(out[9], gemm_ny(c.cols));
+    out[10] = std::max(out[10], gemm_chunks(c.K));
+  };
+  for (int k = 0; k < s.n_lin; ++k) add(fwd_call(s, k));
+  for (int k = s.n_lin - 1; k >= 1; --k) add(bwd_call(s, k));
+  add(bwd_first_call(s));
 }
 
 // the inverse transform's reverse mode always runs layer at a time
@@ -1448,7 +1583,7 @@ struct Runner {
         plain(blob_view(s_, prepared).W + s_.plain_region),
         geom(geo(s_)), B(B_), st(st_), D(s_.D), DT(s_.DT), DC(s_.DC), NL(s_.n_lin), L(s_.L),
         PL(s_.layer_floats), PS(al64(s_.layer_floats)), Dp(geo(s_).Dp),
-        wave_blocks((unsigned)std::min<int64_t>((B_ + 3) / 4, 16384)) {}
+        wave_blocks(wave_grid(B_)) {}
 
   float* Xs(int slot) const { return W + p.stash + (int64_t)slot * B * Dp; }
   float* Hb(int slot, int n, int k) const {
@@ -1487,8 +1622,8 @@ struct Runner {
         j.ones = !last;
         j.act = act(n);
       }
-      gemm(ga, B, ga.job[0].ldw, lin_in(s, k), s.nets, true, last ? kEpiBias : kEpiBiasRelu,
-           false, st);
+      const GemmCall c = fwd_call(s, k);
+      gemm(ga, B, c.cols, c.K, c.nz, c.bt, c.epi, c.pair, st);
     }
   }
 
@@ -1513,7 +1648,8 @@ struct Runner {
         j.ldm = hp(s, k - 1);
         j.act = act(n);
       }
-      gemm(ga, B, gp(s, k - 1), lin_out(s, k), s.nets, false, kEpiMask, false, st);
+      const GemmCall c = bwd_call(s, k);
+      gemm(ga, B, c.cols, c.K, c.nz, c.bt, c.epi, c.pair, st);
     }
     GemmArgs ga{};
     ga.M = B;
@@ -1535,7 +1671,8 @@ struct Runner {
     j.zlt = s.strict ? DT : 0;
     j.ldc = D;
     j.ldw = j.N;
-    gemm(ga, B, j.N, j.K, 1, false, kEpiAdd, s.nets == 2, st);
+    const GemmCall c = bwd_first_call(s);
+    gemm(ga, B, c.cols, c.K, c.nz, c.bt, c.epi, c.pair, st);
   }
 
   // weight / bias gradients of every Linear of both nets (one launch) into the
@@ -1554,7 +1691,7 @@ struct Runner {
     da.M = B;
     da.rows = p.rows_kb;
     da.PS = PS;
-    int jobs = 0, max_subs = 1;
+    int jobs = 0;
     for (int n = 0; n < s.nets; ++n) {
       for (int k = 0; k < NL; ++k) {
         DwJob& j = da.job[jobs++];
@@ -1580,12 +1717,11 @@ struct Runner {
         j.gcl = j.N - 1;
         j.hcl = (int)j.ldh - 1;
         j.slot = 0;
-        const int ncg = ((j.K + 1 + 15) / 16 + kDw16CT - 1) / kDw16CT;
-        max_subs = std::max(max_subs, ((j.N + 127) / 128) * ncg);
       }
     }
     hipLaunchKernelGGL(k_wdw16,
-                       dim3((unsigned)p.nkb, (unsigned)jobs, (unsigned)max_subs), dim3(256), 0, st,
+                       dim3((unsigned)p.nkb, (unsigned)jobs, (unsigned)layer_dw16_subs(s)),
+                       dim3(256), 0, st,
                        da);
     reduce_partials(part, (int)p.nkb, (int)PS, (int)PL, grads_layer, nullptr, st);
     return CNF_OK;

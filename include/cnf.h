@@ -684,6 +684,42 @@ const char* cnf_kernel_name(const cnf_desc* desc);
  * invalid descriptor). */
 const char* cnf_vjp_kernel_name(const cnf_desc* desc);
 
+/* What cnf_vjp / cnf_loss_vjp (inverse = 0) or cnf_vjp_inverse (inverse = 1)
+ * launches for this descriptor on B rows (host only, no HIP call), every word
+ * computed by the function the launch itself uses.  B == 0 reports B == 1 (no
+ * kernel runs).  out[0] is the path, judged at B (cnf_vjp_kernel_name judges
+ * wide-fused at B = 1); words a path does not name are 0.
+ *   layerwise (the inverse's reverse mode is always layerwise):
+ *     [1] kNJ of k_wfwd_update / k_wbwd_update (0 for the inverse, whose update
+ *         kernels loop over the columns), [2] keep_acts (0: the backward sweep
+ *         recomputes the conditioner activations), [3] nkb row blocks of the
+ *         weight gradients, [4] rows per block, [5] k_wseed blocks, [6] blocks
+ *         of the one-wave-per-row kernels, [7] k_wdw16's grid z,
+ *     [8] the k_wgemm instantiations of a layer's sweeps, bit 2 f + (NC - 1)
+ *         with f the (BT, EPI, PAIR) form: 0 forward bias, 1 forward bias +
+ *         activation, 2 back-prop with the activation's derivative, 3 the
+ *         first Linear's back-prop of both nets (PAIR), 4 of one net,
+ *     [9] the most column blocks (ny) and [10] the most reduction chunks of
+ *         128 over those launches.  Words 7-10 are 0 without a conditioner.
+ *   wide-fused:
+ *     [1] the row of k_wide16's table, [2] nets, [3] nkb, [4] rows per block,
+ *     [5] k_wseed blocks (generic seeds), [6] 1: the weight gradients run on
+ *     k_wdw16g, 0: on k_wdw16 with [7] its grid z, [8] the k_wdw16g classes
+ *     (G tiles, H tiles) of the layer's jobs, bit i the i-th class of
+ *     (7,4) (7,7) (4,7) (4,4) (4,2) (4,5) (1,5).
+ * Errors as cnf_vjp_workspace_bytes, except that an unsupported reverse mode
+ * is CNF_OK with path CNF_VJP_PATH_NONE; inverse outside {0, 1}: CNF_ERR_DESC. */
+#define CNF_VJP_PLAN_WORDS 16
+enum {
+  CNF_VJP_PATH_NONE = 0,
+  CNF_VJP_PATH_VJP2 = 1,
+  CNF_VJP_PATH_ROWS = 2,
+  CNF_VJP_PATH_LAYERWISE = 3,
+  CNF_VJP_PATH_WIDE_FUSED = 4
+};
+int cnf_vjp_launch_plan(const cnf_desc* desc, int64_t B, int32_t inverse,
+                        int32_t out[CNF_VJP_PLAN_WORDS]);
+
 const char* cnf_strerror(int status);
 /* The hipError_t behind the last CNF_ERR_HIP on this thread. */
 int cnf_last_hip_error(void);

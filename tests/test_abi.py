@@ -84,6 +84,42 @@ def test_vjp_kernel_selection():
     assert stack.vjp_kernel_name() == "vjp2"
 
 
+def test_vjp_launch_plan_paths_and_argument_checks():
+    """cnf_vjp_launch_plan (host only): the path word for every path, and its
+    argument errors; tests/test_widesweep_sync_cpu.py holds the other words."""
+    lib = _lib.lib()
+    out = (ctypes.c_int32 * _lib.VJP_PLAN_WORDS)()
+
+    def path(d, B=8, inverse=0):
+        for i in range(_lib.VJP_PLAN_WORDS):
+            out[i] = -7
+        assert lib.cnf_vjp_launch_plan(ctypes.byref(d), ctypes.c_int64(B),
+                                       ctypes.c_int32(inverse), out) == 0
+        return _lib.VJP_PATHS[out[0]], list(out)[1:]
+
+    assert path(_lib.make_desc(10, 6, [5, 5])) == ("vjp2", [0] * 15)
+    assert path(_lib.make_desc(10, 12, [5, 5])) == ("vjp-rows", [0] * 15)
+    assert path(_lib.make_desc(10, 6, [5, 5]), inverse=1)[0] == "layerwise"   # wvjp_inv_run
+    assert path(_lib.make_desc(10, 6, [10, 10]))[0] == "layerwise"
+    assert path(_lib.make_desc(100, 12, [100, 100]))[0] == "wide-fused"
+    assert path(_lib.make_desc(100, 12, [100, 100]), inverse=1)[0] == "layerwise"
+    assert path(_lib.make_desc(256, 2, [512])) == ("none", [0] * 15)
+    assert path(_lib.make_desc(17, 2, []), B=0) == path(_lib.make_desc(17, 2, []), B=1)
+    stack = CouplingStack([NvpCouplingLayer(10, [5, 5]) for _ in range(3)])
+    assert stack.vjp_launch_plan(8) == {"path": "vjp2"}
+    d = _lib.make_desc(100, 2, [100])
+    I64, I32 = ctypes.c_int64, ctypes.c_int32
+    assert lib.cnf_vjp_launch_plan(None, I64(8), I32(0), out) == -1          # CNF_ERR_NULL
+    assert lib.cnf_vjp_launch_plan(ctypes.byref(d), I64(8), I32(0), None) == -1
+    assert lib.cnf_vjp_launch_plan(ctypes.byref(d), I64(-1), I32(0), out) == -4   # CNF_ERR_BATCH
+    assert lib.cnf_vjp_launch_plan(ctypes.byref(d), I64(8), I32(2), out) == -2    # CNF_ERR_DESC
+    bad = _lib.make_desc(100, 2, [100])
+    bad.abi_version = 99
+    assert lib.cnf_vjp_launch_plan(ctypes.byref(bad), I64(8), I32(0), out) == -2
+    bad = _lib.make_desc(1000, 2, [100])
+    assert lib.cnf_vjp_launch_plan(ctypes.byref(bad), I64(8), I32(0), out) == -3  # past CNF_MAX_DIM
+
+
 def test_legacy_kernel_family_selection():
     """Legacy stacks (CNF_OPT_ALT_MASK / S_TANH) of k_valu's shapes run on k_valu
     (never on k_sgpr), the rest on the MFMA-tile family."""

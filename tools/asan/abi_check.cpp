@@ -80,6 +80,8 @@ int main(int argc, char** argv) {
     EXPECT(is_status(cnf_forward_loss_workspace_bytes(&d, B, &ws)));
     EXPECT(is_status(cnf_vjp_workspace_bytes(&d, B, &ws)));
     EXPECT(is_status(cnf_vjp_inverse_workspace_bytes(&d, B, &ws)));
+    int32_t plan[CNF_VJP_PLAN_WORDS];
+    EXPECT(is_status(cnf_vjp_launch_plan(&d, B, U(0, 1), plan)));
     if (s0 == CNF_OK) {
       ++n_ok;
       // an empty stack (no s- and no t-net) has no parameters
