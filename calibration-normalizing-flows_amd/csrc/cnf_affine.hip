@@ -627,197 +627,79 @@ __global__ __launch_bounds__(kFinThreads) void k_affine_finish(
 
 // ---- launches -------------------------------------------------------------------
 
-template <int LPR, int CPL>
-void launch_fwd(int blocks, hipStream_t s, const float* x, const float* blob, int D, int L, int cs,
-                int64_t B, float* z, float* z_all, float* ld, const int64_t* y, int kind,
-                float ldw, float* part, int inv) {
-  hipLaunchKernelGGL((k_affine_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, D, L,
-                     cs, B, z, z_all, ld, y, kind, ldw, part, inv);
-}
-
-template <int LPR, int CPL>
-void launch_predict(int blocks, hipStream_t s, const float* x, const float* blob, const float* lp,
-                    int D, int L, int cs, int64_t B, float* probs, const score::Args* sc) {
-  if (sc) {
-    hipLaunchKernelGGL((k_affine_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, s, x,
-                       blob, lp, D, L, cs, B, (float*)nullptr, *sc);
-  } else {
-    hipLaunchKernelGGL((k_affine_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, s, x,
-                       blob, lp, D, L, cs, B, probs, score::Args{});
-  }
-}
-
-template <int LPR, int CPL>
-void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (!affine_bwd_variant(LPR, CPL, a.L).regt) {
-    hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-    return;
-  }
-  // rega depends on the depth through regt alone: the geometry's answer at kRegL
-  if constexpr (affine_bwd_variant(LPR, CPL, kRegL).rega) {
-    hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-  } else {
-    hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-  }
-}
-
-int check_shape(int32_t dim, int32_t n_layers) {
-  return rowflow::check_shape(dim, n_layers, kMaxL);
-}
-
-// Common argument checks; fills the pointer table.
-int check_common(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
-                 int64_t B, const void* ws, size_t ws_bytes, Ptrs* P, Geo* g, Plan* p) {
-  return rowflow::check_common(kFamily, dim, n_layers, params, x, B, ws, ws_bytes, P->p, g, p);
-}
-
-int run_prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool inv, hipStream_t s) {
-  hipLaunchKernelGGL(k_affine_prep, dim3(1), dim3(kThreads), 0, s, P, blob, D, g.dp, g.cs, L,
-                     inv ? 1 : 0);
-  return launch_status();
-}
-
 // the loss's weight of the log-det
 float ld_weight(int32_t kind, float det) { return kind == CNF_LOSS_CAL ? 1.f : det; }
 
-int run_forward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                int32_t kind, float det, float* z, float* ld, float* z_all, float* terms, int64_t B,
-                void* ws, size_t ws_bytes, hipStream_t s, bool loss, bool inv) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
-  }
-  if (mis4(z) || mis4(z_all) || mis4(ld)) return CNF_ERR_ALIGN;
-  if (B == 0) {  // no row: the terms are 0; the log-det is not formed without a launch
-    if (loss) st = hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s));
-    if (st == CNF_OK && ld) st = hip_status(hipMemsetAsync(ld, 0, sizeof(float), s));
-    return st;
-  }
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, inv, s);
-  if (st != CNF_OK) return st;
-  const int blocks = fwd_blocks(g, B);
-  float* part = loss ? w + p.part : nullptr;
-  CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, z_all, ld,
-                       loss ? y : nullptr, kind, ld_weight(kind, det), part, inv ? 1 : 0);
-  st = launch_status();
-  if (st != CNF_OK || !loss) return st;
-  hipLaunchKernelGGL(k_affine_finish, dim3(1), dim3(kFinThreads), 0, s, part, blocks, 4, 0,
-                     w + p.sums, terms, (float*)nullptr, (const float*)nullptr, 0.f, D, L);
-  return launch_status();
-}
+// What cnf_rowflow.h's launch layer asks of a family.
+struct Affine {
+  using Table = Ptrs;
+  using Args = BwdArgs;
+  static constexpr bool kLdScalar = true;  // the log-det is one number: [1]
+  static const RowFamily& family() { return kFamily; }
+  static constexpr int grad_floats(int D) { return 2 * D; }  // s, t
 
-// predict (sc == null) or score
-int run_predict(int32_t D, int32_t L, const float* const* params, const float* x, const float* lp,
-                float* probs, const int64_t* y, int32_t bins, int64_t* record, int64_t B, void* ws,
-                size_t ws_bytes, hipStream_t s, bool scoring) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_shape(D, L);
-  if (st != CNF_OK) return st;
-  if (scoring) {
-    st = score::check_args(D, bins, B, y, record);
-    if (st != CNF_OK) return st;
+  static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool inv,
+                   hipStream_t s) {
+    hipLaunchKernelGGL(k_affine_prep, dim3(1), dim3(kThreads), 0, s, P, blob, D, g.dp, g.cs, L,
+                       inv ? 1 : 0);
   }
-  st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (B > 0 && (!lp || (!scoring && !probs))) return CNF_ERR_NULL;
-  if (mis4(lp) || mis4(probs)) return CNF_ERR_ALIGN;
-  if (B == 0) return CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, false, s);
-  if (st != CNF_OK) return st;
-  score::Args sc;
-  if (scoring) sc = score::make_args(y, bins, record);
-  CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
-                       scoring ? &sc : nullptr);
-  return launch_status();
-}
 
-int run_backward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                 int32_t kind, float det, float gscale, const float* gz, const float* gz_all,
-                 const float* gld, float* terms, float* grads, float* dx, int64_t B, void* ws,
-                 size_t ws_bytes, hipStream_t s, bool loss) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (!grads) return CNF_ERR_NULL;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  template <int LPR, int CPL>
+  static void fwd(int blocks, const FwdCall& c, const Geo& g, const float* blob, float* part) {
+    hipLaunchKernelGGL((k_affine_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x, blob,
+                       c.D, c.L, g.cs, c.B, c.z, c.z_all, c.ld, c.y, c.kind,
+                       ld_weight(c.kind, c.det), part, c.inv ? 1 : 0);
   }
-  if (mis4(gz) || mis4(gz_all) || mis4(gld) || mis4(grads) || mis4(dx)) return CNF_ERR_ALIGN;
-  const size_t gbytes = (size_t)L * 2 * D * sizeof(float);
-  if (B == 0) {
-    st = hip_status(hipMemsetAsync(grads, 0, gbytes, s));
-    if (st == CNF_OK && loss) st = hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s));
-    return st;
+
+  template <int LPR, int CPL>
+  static void predict(int blocks, const PredictCall& c, const Geo& g, const float* blob,
+                      const score::Args* sc) {
+    if (sc) {
+      hipLaunchKernelGGL((k_affine_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, (float*)nullptr, *sc);
+    } else {
+      hipLaunchKernelGGL((k_affine_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, c.probs, score::Args{});
+    }
   }
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, false, s);
-  if (st != CNF_OK) return st;
-  const int blocks = bwd_blocks(g, B);
-  const int units = bwd_units(g, B);
-  size_t lds = 0;
-  if (g.gacc) {
-    st = hip_status(hipMemsetAsync(w + p.part, 0, (size_t)units * g.pw * sizeof(float), s));
-    if (st != CNF_OK) return st;
-  } else {
-    lds = (size_t)kWaves * g.pw * sizeof(float);
+
+  template <int LPR, int CPL>
+  static void bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
+    if (!affine_bwd_variant(LPR, CPL, a.L).regt) {
+      hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a, a.blob);
+      return;
+    }
+    // rega depends on the depth through regt alone: the geometry's answer at kRegL
+    if constexpr (affine_bwd_variant(LPR, CPL, kRegL).rega) {
+      hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds,
+                         s, a, a.blob);
+    } else {
+      hipLaunchKernelGGL((k_affine_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a, a.blob);
+    }
   }
-  const float ldw = ld_weight(kind, det);
-  BwdArgs a;
-  a.x = x;
-  a.blob = w + p.blob;
-  a.y = loss ? y : nullptr;
-  a.gz = loss ? nullptr : gz;
-  a.gz_all = loss ? nullptr : gz_all;
-  a.dx = dx;
-  a.part = w + p.part;
-  a.B = B;
-  a.D = D;
-  a.L = L;
-  a.cs = g.cs;
-  a.ps = g.ps;
-  a.pw = g.pw;
-  a.gacc = g.gacc ? 1 : 0;
-  a.kind = kind;
-  a.ldw = ldw;
-  a.gscale = gscale;
-  CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, s, a);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  // every row's loss holds -ldw * ld: the log-det's gradient is the rows' sum of it
-  const float gldv = loss ? (float)(-(double)ldw * (double)gscale * (double)B) : 0.f;
-  hipLaunchKernelGGL(k_affine_finish, dim3(1), dim3(kFinThreads), 0, s, a.part, units, g.pw,
-                     L * g.ps, w + p.sums, loss ? terms : (float*)nullptr, grads,
-                     loss ? (const float*)nullptr : gld, gldv, D, L);
-  return launch_status();
-}
+
+  static void fill(BwdArgs& a, const BwdCall& c, float*) { a.ldw = ld_weight(c.kind, c.det); }
+
+  // c: the reverse call whose gradients this writes, null after a forward
+  static void finish(const Finish& f, const Ptrs&, int D, int L, const Geo&, const BwdCall* c,
+                     hipStream_t s) {
+    // every row's loss holds -ldw * ld: the log-det's gradient is the rows' sum of it
+    const bool loss = c && c->loss;
+    const float ldw = loss ? ld_weight(c->kind, c->det) : 0.f;
+    const float gldv = loss ? (float)(-(double)ldw * (double)c->gscale * (double)c->B) : 0.f;
+    const float* gld = c && !loss ? c->gld : nullptr;
+    hipLaunchKernelGGL(k_affine_finish, dim3(1), dim3(kFinThreads), 0, s, f.part, f.units, f.pw,
+                       f.nsum, f.sums, f.terms, f.grads, gld, gldv, D, L);
+  }
+};
 
 }  // namespace
 }  // namespace cnf
 
 extern "C" int cnf_affine_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats) {
-  using namespace cnf;
-  if (!n_floats) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers);
-  if (st != CNF_OK) return st;
-  *n_floats = (int64_t)n_layers * 2 * dim;
-  return CNF_OK;
+  return cnf::rowflow::param_count(cnf::kFamily, cnf::Affine::grad_floats, dim, n_layers, n_floats);
 }
 
 extern "C" int cnf_affine_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
@@ -833,16 +715,20 @@ extern "C" int cnf_affine_forward(int32_t dim, int32_t n_layers, const float* co
                                   const float* x, float* z, float* logdet, float* z_all, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_affine_forward");
-  return cnf::run_forward(dim, n_layers, params, x, nullptr, 0, 0.f, z, logdet, z_all, nullptr, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, false, false);
+  return cnf::rowflow::run_forward<cnf::Affine>({dim, n_layers, params, x, nullptr, 0, 0.f, z,
+                                                 logdet, z_all, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false,
+                                                 false});
 }
 
 extern "C" int cnf_affine_inverse(int32_t dim, int32_t n_layers, const float* const* params,
                                   const float* z, float* x, float* logdet, float* x_all, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_affine_inverse");
-  return cnf::run_forward(dim, n_layers, params, z, nullptr, 0, 0.f, x, logdet, x_all, nullptr, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, false, true);
+  return cnf::rowflow::run_forward<cnf::Affine>({dim, n_layers, params, z, nullptr, 0, 0.f, x,
+                                                 logdet, x_all, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false,
+                                                 true});
 }
 
 extern "C" int cnf_affine_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
@@ -851,17 +737,19 @@ extern "C" int cnf_affine_forward_loss(int32_t dim, int32_t n_layers, const floa
                                        int64_t B, void* workspace, size_t workspace_bytes,
                                        void* stream) {
   CNF_RANGE("cnf_affine_forward_loss");
-  return cnf::run_forward(dim, n_layers, params, x, y, loss_kind, det, z, logdet, nullptr,
-                          loss_terms, B, workspace, workspace_bytes, (hipStream_t)stream, true,
-                          false);
+  return cnf::rowflow::run_forward<cnf::Affine>({dim, n_layers, params, x, y, loss_kind, det, z,
+                                                 logdet, nullptr, loss_terms, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true,
+                                                 false});
 }
 
 extern "C" int cnf_affine_predict(int32_t dim, int32_t n_layers, const float* const* params,
                                   const float* x, const float* log_priors, float* probs, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_affine_predict");
-  return cnf::run_predict(dim, n_layers, params, x, log_priors, probs, nullptr, 0, nullptr, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_predict<cnf::Affine>({dim, n_layers, params, x, log_priors, probs,
+                                                 nullptr, nullptr, 0, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false});
 }
 
 extern "C" int cnf_affine_score(int32_t dim, int32_t n_layers, const float* const* params,
@@ -869,8 +757,9 @@ extern "C" int cnf_affine_score(int32_t dim, int32_t n_layers, const float* cons
                                 int32_t bins, int64_t* record, int64_t B, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_affine_score");
-  return cnf::run_predict(dim, n_layers, params, x, log_priors, nullptr, y, bins, record, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, true);
+  return cnf::rowflow::run_predict<cnf::Affine>({dim, n_layers, params, x, log_priors, nullptr,
+                                                 nullptr, y, bins, record, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true});
 }
 
 extern "C" int cnf_affine_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -878,9 +767,9 @@ extern "C" int cnf_affine_vjp(int32_t dim, int32_t n_layers, const float* const*
                               const float* gld, float* grads, float* dx, int64_t B,
                               void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_affine_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, nullptr, 0, 0.f, 1.f, gz, gz_all, gld,
-                           nullptr, grads, dx, B, workspace, workspace_bytes, (hipStream_t)stream,
-                           false);
+  return cnf::rowflow::run_backward<cnf::Affine>({dim, n_layers, params, x, nullptr, 0, 0.f, 1.f,
+                                                  gz, gz_all, gld, nullptr, grads, dx, B, workspace,
+                                                  workspace_bytes, (hipStream_t)stream, false});
 }
 
 extern "C" int cnf_affine_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -889,7 +778,8 @@ extern "C" int cnf_affine_loss_vjp(int32_t dim, int32_t n_layers, const float* c
                                    int64_t B, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   CNF_RANGE("cnf_affine_loss_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, y, loss_kind, det, grad_scale, nullptr,
-                           nullptr, nullptr, loss_terms, grads, dx, B, workspace, workspace_bytes,
-                           (hipStream_t)stream, true);
+  return cnf::rowflow::run_backward<cnf::Affine>({dim, n_layers, params, x, y, loss_kind, det,
+                                                  grad_scale, nullptr, nullptr, nullptr, loss_terms,
+                                                  grads, dx, B, workspace, workspace_bytes,
+                                                  (hipStream_t)stream, true});
 }

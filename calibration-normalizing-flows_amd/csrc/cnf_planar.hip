@@ -590,203 +590,71 @@ __global__ __launch_bounds__(kFinThreads) void k_planar_finish(
 
 // ---- launches -------------------------------------------------------------------
 
-template <int LPR, int CPL>
-void launch_fwd(int blocks, hipStream_t s, const float* x, const float* blob, int D, int L, int cs,
-                int64_t B, float* z, float* ld, float* z_all, const int64_t* y, int kind, float det,
-                float* part) {
-  hipLaunchKernelGGL((k_planar_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, D, L,
-                     cs, B, z, ld, z_all, y, kind, det, part);
-}
+// What cnf_rowflow.h's launch layer asks of a family.
+struct Planar {
+  using Table = Ptrs;
+  using Args = BwdArgs;
+  static constexpr bool kLdScalar = false;  // the log-det is a row's: [B]
+  static const RowFamily& family() { return kFamily; }
+  static constexpr int grad_floats(int D) { return 2 * D + 1; }  // w, u, b
 
-template <int LPR, int CPL>
-void launch_predict(int blocks, hipStream_t s, const float* x, const float* blob, const float* lp,
-                    int D, int L, int cs, int64_t B, float* probs, float* ld) {
-  hipLaunchKernelGGL((k_planar_predict<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, lp,
-                     D, L, cs, B, probs, ld);
-}
-
-template <int LPR, int CPL>
-void launch_score(int blocks, hipStream_t s, const float* x, const float* blob, const float* lp,
-                  int D, int L, int cs, int64_t B, const score::Args& sc) {
-  hipLaunchKernelGGL((k_planar_score<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, lp, D,
-                     L, cs, B, sc);
-}
-
-template <int LPR, int CPL>
-void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (!planar_bwd_variant(LPR, CPL, a.L).regt) {
-    hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
-    return;
+  static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool, hipStream_t s) {
+    hipLaunchKernelGGL(k_planar_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);
   }
-  // rega depends on the depth through regt alone: the geometry's answer at kRegL
-  if constexpr (planar_bwd_variant(LPR, CPL, kRegL).rega) {
-    hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
-  } else {
-    hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
+
+  template <int LPR, int CPL>
+  static void fwd(int blocks, const FwdCall& c, const Geo& g, const float* blob, float* part) {
+    hipLaunchKernelGGL((k_planar_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x, blob,
+                       c.D, c.L, g.cs, c.B, c.z, c.ld, c.z_all, c.y, c.kind, c.det, part);
   }
-}
 
-int check_shape(int32_t dim, int32_t n_layers) {
-  return rowflow::check_shape(dim, n_layers, kMaxL);
-}
-
-// Common argument checks; fills the pointer table.
-int check_common(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
-                 int64_t B, const void* ws, size_t ws_bytes, Ptrs* P, Geo* g, Plan* p) {
-  return rowflow::check_common(kFamily, dim, n_layers, params, x, B, ws, ws_bytes, P->p, g, p);
-}
-
-int run_prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, hipStream_t s) {
-  hipLaunchKernelGGL(k_planar_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);
-  return launch_status();
-}
-
-int run_forward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                int32_t kind, float det, float* z, float* ld, float* z_all, float* terms, int64_t B,
-                void* ws, size_t ws_bytes, hipStream_t s, bool loss) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  template <int LPR, int CPL>
+  static void predict(int blocks, const PredictCall& c, const Geo& g, const float* blob,
+                      const score::Args* sc) {
+    if (sc) {
+      hipLaunchKernelGGL((k_planar_score<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x,
+                         blob, c.lp, c.D, c.L, g.cs, c.B, *sc);
+    } else {
+      hipLaunchKernelGGL((k_planar_predict<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x,
+                         blob, c.lp, c.D, c.L, g.cs, c.B, c.probs, c.ld);
+    }
   }
-  if (mis4(z) || mis4(ld) || mis4(z_all)) return CNF_ERR_ALIGN;
-  if (B == 0) return loss ? hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s)) : CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  const int blocks = fwd_blocks(g, B);
-  float* part = loss ? w + p.part : nullptr;
-  CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, ld, z_all,
-                       loss ? y : nullptr, kind, det, part);
-  st = launch_status();
-  if (st != CNF_OK || !loss) return st;
-  hipLaunchKernelGGL(k_planar_finish, dim3(1), dim3(kFinThreads), 0, s, part, blocks, 4, 0,
-                     w + p.sums, terms, (float*)nullptr, w + p.blob, P, D, L, g.dp, g.cs);
-  return launch_status();
-}
 
-int run_predict(int32_t D, int32_t L, const float* const* params, const float* x, const float* lp,
-                float* probs, float* ld, int64_t B, void* ws, size_t ws_bytes, hipStream_t s) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (B > 0 && (!lp || !probs)) return CNF_ERR_NULL;
-  if (mis4(lp) || mis4(probs) || mis4(ld)) return CNF_ERR_ALIGN;
-  if (B == 0) return CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
-                       ld);
-  return launch_status();
-}
+  template <int LPR, int CPL>
+  static void bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
+    if (!planar_bwd_variant(LPR, CPL, a.L).regt) {
+      hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+      return;
+    }
+    // rega depends on the depth through regt alone: the geometry's answer at kRegL
+    if constexpr (planar_bwd_variant(LPR, CPL, kRegL).rega) {
+      hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+    } else {
+      hipLaunchKernelGGL((k_planar_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+    }
+  }
 
-int run_score(int32_t D, int32_t L, const float* const* params, const float* x, const float* lp,
-              const int64_t* y, int32_t bins, int64_t* record, int64_t B, void* ws, size_t ws_bytes,
-              hipStream_t s) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_shape(D, L);
-  if (st != CNF_OK) return st;
-  st = score::check_args(D, bins, B, y, record);
-  if (st != CNF_OK) return st;
-  st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (B > 0 && !lp) return CNF_ERR_NULL;
-  if (mis4(lp)) return CNF_ERR_ALIGN;
-  if (B == 0) return CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  const score::Args sc = score::make_args(y, bins, record);
-  CNF_ROWFLOW_DISPATCH(launch_score, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, sc);
-  return launch_status();
-}
+  static void fill(BwdArgs& a, const BwdCall& c, float* tape) {
+    a.gld = c.loss ? nullptr : c.gld;
+    a.tape = tape;
+    a.det = c.det;
+  }
 
-int run_backward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                 int32_t kind, float det, float gscale, const float* gz, const float* gz_all,
-                 const float* gld, float* terms, float* grads, float* dx, int64_t B, void* ws,
-                 size_t ws_bytes, hipStream_t s, bool loss) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (!grads) return CNF_ERR_NULL;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  static void finish(const Finish& f, const Ptrs& P, int D, int L, const Geo& g, const BwdCall*,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_planar_finish, dim3(1), dim3(kFinThreads), 0, s, f.part, f.units, f.pw,
+                       f.nsum, f.sums, f.terms, f.grads, f.blob, P, D, L, g.dp, g.cs);
   }
-  if (mis4(gz) || mis4(gz_all) || mis4(gld) || mis4(grads) || mis4(dx)) return CNF_ERR_ALIGN;
-  const size_t gbytes = (size_t)L * (2 * D + 1) * sizeof(float);
-  if (B == 0) {
-    st = hip_status(hipMemsetAsync(grads, 0, gbytes, s));
-    if (st == CNF_OK && loss) st = hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s));
-    return st;
-  }
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  const int blocks = bwd_blocks(g, B);
-  const int units = bwd_units(g, B);
-  size_t lds = 0;
-  if (g.gacc) {
-    st = hip_status(hipMemsetAsync(w + p.part, 0, (size_t)units * g.pw * sizeof(float), s));
-    if (st != CNF_OK) return st;
-  } else {
-    lds = (size_t)kWaves * g.pw * sizeof(float);
-  }
-  BwdArgs a;
-  a.x = x;
-  a.blob = w + p.blob;
-  a.y = loss ? y : nullptr;
-  a.gz = loss ? nullptr : gz;
-  a.gz_all = loss ? nullptr : gz_all;
-  a.gld = loss ? nullptr : gld;
-  a.dx = dx;
-  a.part = w + p.part;
-  a.tape = w + p.tape;
-  a.B = B;
-  a.D = D;
-  a.L = L;
-  a.cs = g.cs;
-  a.ps = g.ps;
-  a.pw = g.pw;
-  a.gacc = g.gacc ? 1 : 0;
-  a.kind = kind;
-  a.det = det;
-  a.gscale = gscale;
-  CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, s, a);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  hipLaunchKernelGGL(k_planar_finish, dim3(1), dim3(kFinThreads), 0, s, a.part, units, g.pw,
-                     L * g.ps, w + p.sums, loss ? terms : (float*)nullptr, grads, w + p.blob, P, D,
-                     L, g.dp, g.cs);
-  return launch_status();
-}
+};
 
 }  // namespace
 }  // namespace cnf
 
 extern "C" int cnf_planar_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats) {
-  using namespace cnf;
-  if (!n_floats) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers);
-  if (st != CNF_OK) return st;
-  *n_floats = (int64_t)n_layers * (2 * dim + 1);
-  return CNF_OK;
+  return cnf::rowflow::param_count(cnf::kFamily, cnf::Planar::grad_floats, dim, n_layers, n_floats);
 }
 
 extern "C" int cnf_planar_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
@@ -802,8 +670,10 @@ extern "C" int cnf_planar_forward(int32_t dim, int32_t n_layers, const float* co
                                   const float* x, float* z, float* logdet, float* z_all, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_planar_forward");
-  return cnf::run_forward(dim, n_layers, params, x, nullptr, 0, 0.f, z, logdet, z_all, nullptr, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_forward<cnf::Planar>({dim, n_layers, params, x, nullptr, 0, 0.f, z,
+                                                 logdet, z_all, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false,
+                                                 false});
 }
 
 extern "C" int cnf_planar_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
@@ -812,8 +682,10 @@ extern "C" int cnf_planar_forward_loss(int32_t dim, int32_t n_layers, const floa
                                        int64_t B, void* workspace, size_t workspace_bytes,
                                        void* stream) {
   CNF_RANGE("cnf_planar_forward_loss");
-  return cnf::run_forward(dim, n_layers, params, x, y, loss_kind, det, z, logdet, nullptr,
-                          loss_terms, B, workspace, workspace_bytes, (hipStream_t)stream, true);
+  return cnf::rowflow::run_forward<cnf::Planar>({dim, n_layers, params, x, y, loss_kind, det, z,
+                                                 logdet, nullptr, loss_terms, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true,
+                                                 false});
 }
 
 extern "C" int cnf_planar_predict(int32_t dim, int32_t n_layers, const float* const* params,
@@ -821,8 +693,9 @@ extern "C" int cnf_planar_predict(int32_t dim, int32_t n_layers, const float* co
                                   float* logdet, int64_t B, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_planar_predict");
-  return cnf::run_predict(dim, n_layers, params, x, log_priors, probs, logdet, B, workspace,
-                          workspace_bytes, (hipStream_t)stream);
+  return cnf::rowflow::run_predict<cnf::Planar>({dim, n_layers, params, x, log_priors, probs,
+                                                 logdet, nullptr, 0, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false});
 }
 
 extern "C" int cnf_planar_score(int32_t dim, int32_t n_layers, const float* const* params,
@@ -830,8 +703,9 @@ extern "C" int cnf_planar_score(int32_t dim, int32_t n_layers, const float* cons
                                 int32_t bins, int64_t* record, int64_t B, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_planar_score");
-  return cnf::run_score(dim, n_layers, params, x, log_priors, y, bins, record, B, workspace,
-                        workspace_bytes, (hipStream_t)stream);
+  return cnf::rowflow::run_predict<cnf::Planar>({dim, n_layers, params, x, log_priors, nullptr,
+                                                 nullptr, y, bins, record, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true});
 }
 
 extern "C" int cnf_planar_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -839,8 +713,9 @@ extern "C" int cnf_planar_vjp(int32_t dim, int32_t n_layers, const float* const*
                               const float* gld, float* grads, float* dx, int64_t B, void* workspace,
                               size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_planar_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, nullptr, 0, 0.f, 1.f, gz, gz_all, gld, nullptr,
-                           grads, dx, B, workspace, workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_backward<cnf::Planar>({dim, n_layers, params, x, nullptr, 0, 0.f, 1.f,
+                                                  gz, gz_all, gld, nullptr, grads, dx, B, workspace,
+                                                  workspace_bytes, (hipStream_t)stream, false});
 }
 
 extern "C" int cnf_planar_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -849,7 +724,8 @@ extern "C" int cnf_planar_loss_vjp(int32_t dim, int32_t n_layers, const float* c
                                    int64_t B, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   CNF_RANGE("cnf_planar_loss_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, y, loss_kind, det, grad_scale, nullptr, nullptr,
-                           nullptr, loss_terms, grads, dx, B, workspace, workspace_bytes,
-                           (hipStream_t)stream, true);
+  return cnf::rowflow::run_backward<cnf::Planar>({dim, n_layers, params, x, y, loss_kind, det,
+                                                  grad_scale, nullptr, nullptr, nullptr, loss_terms,
+                                                  grads, dx, B, workspace, workspace_bytes,
+                                                  (hipStream_t)stream, true});
 }

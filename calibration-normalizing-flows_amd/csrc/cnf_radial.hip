@@ -631,185 +631,67 @@ __global__ __launch_bounds__(kFinThreads) void k_radial_finish(
 
 // ---- launches -------------------------------------------------------------------
 
-template <int LPR, int CPL>
-void launch_fwd(int blocks, hipStream_t s, const float* x, const float* blob, int D, int L, int cs,
-                int64_t B, float* z, float* z_all, const int64_t* y, int kind, float* part) {
-  hipLaunchKernelGGL((k_radial_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, s, x, blob, D, L,
-                     cs, B, z, z_all, y, kind, part);
-}
+// What cnf_rowflow.h's launch layer asks of a family.
+struct Radial {
+  using Table = Ptrs;
+  using Args = BwdArgs;
+  static constexpr bool kLdScalar = false;  // no log-det at all
+  static const RowFamily& family() { return kFamily; }
+  static constexpr int grad_floats(int D) { return D + 2; }  // z0, a, b
 
-template <int LPR, int CPL>
-void launch_predict(int blocks, hipStream_t s, const float* x, const float* blob, const float* lp,
-                    int D, int L, int cs, int64_t B, float* probs, const score::Args* sc) {
-  if (sc) {
-    hipLaunchKernelGGL((k_radial_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, s, x,
-                       blob, lp, D, L, cs, B, (float*)nullptr, *sc);
-  } else {
-    hipLaunchKernelGGL((k_radial_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, s, x,
-                       blob, lp, D, L, cs, B, probs, score::Args{});
+  static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool, hipStream_t s) {
+    hipLaunchKernelGGL(k_radial_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);
   }
-}
 
-template <int LPR, int CPL>
-void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (!radial_bwd_variant(LPR, CPL, a.L).regt) {
-    hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
-    return;
+  template <int LPR, int CPL>
+  static void fwd(int blocks, const FwdCall& c, const Geo& g, const float* blob, float* part) {
+    hipLaunchKernelGGL((k_radial_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x, blob,
+                       c.D, c.L, g.cs, c.B, c.z, c.z_all, c.y, c.kind, part);
   }
-  // rega depends on the depth through regt alone: the geometry's answer at kRegL
-  if constexpr (radial_bwd_variant(LPR, CPL, kRegL).rega) {
-    hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
-  } else {
-    hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a);
-  }
-}
 
-int check_shape(int32_t dim, int32_t n_layers) {
-  return rowflow::check_shape(dim, n_layers, kMaxL);
-}
-
-// Common argument checks; fills the pointer table.
-int check_common(int32_t dim, int32_t n_layers, const float* const* params, const float* x,
-                 int64_t B, const void* ws, size_t ws_bytes, Ptrs* P, Geo* g, Plan* p) {
-  return rowflow::check_common(kFamily, dim, n_layers, params, x, B, ws, ws_bytes, P->p, g, p);
-}
-
-int run_prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, hipStream_t s) {
-  hipLaunchKernelGGL(k_radial_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);
-  return launch_status();
-}
-
-int run_forward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                int32_t kind, float* z, float* z_all, float* terms, int64_t B, void* ws,
-                size_t ws_bytes, hipStream_t s, bool loss) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  template <int LPR, int CPL>
+  static void predict(int blocks, const PredictCall& c, const Geo& g, const float* blob,
+                      const score::Args* sc) {
+    if (sc) {
+      hipLaunchKernelGGL((k_radial_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, (float*)nullptr, *sc);
+    } else {
+      hipLaunchKernelGGL((k_radial_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, c.probs, score::Args{});
+    }
   }
-  if (mis4(z) || mis4(z_all)) return CNF_ERR_ALIGN;
-  if (B == 0) return loss ? hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s)) : CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  const int blocks = fwd_blocks(g, B);
-  float* part = loss ? w + p.part : nullptr;
-  CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, s, x, w + p.blob, D, L, g.cs, B, z, z_all,
-                       loss ? y : nullptr, kind, part);
-  st = launch_status();
-  if (st != CNF_OK || !loss) return st;
-  hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, part, blocks, 4, 0,
-                     w + p.sums, terms, (float*)nullptr, w + p.blob, D, L, g.dp, g.cs);
-  return launch_status();
-}
 
-// predict (sc == null) or score
-int run_predict(int32_t D, int32_t L, const float* const* params, const float* x, const float* lp,
-                float* probs, const int64_t* y, int32_t bins, int64_t* record, int64_t B, void* ws,
-                size_t ws_bytes, hipStream_t s, bool scoring) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_shape(D, L);
-  if (st != CNF_OK) return st;
-  if (scoring) {
-    st = score::check_args(D, bins, B, y, record);
-    if (st != CNF_OK) return st;
+  template <int LPR, int CPL>
+  static void bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
+    if (!radial_bwd_variant(LPR, CPL, a.L).regt) {
+      hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+      return;
+    }
+    // rega depends on the depth through regt alone: the geometry's answer at kRegL
+    if constexpr (radial_bwd_variant(LPR, CPL, kRegL).rega) {
+      hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+    } else {
+      hipLaunchKernelGGL((k_radial_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a);
+    }
   }
-  st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (B > 0 && (!lp || (!scoring && !probs))) return CNF_ERR_NULL;
-  if (mis4(lp) || mis4(probs)) return CNF_ERR_ALIGN;
-  if (B == 0) return CNF_OK;
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  score::Args sc;
-  if (scoring) sc = score::make_args(y, bins, record);
-  CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, B), s, x, w + p.blob, lp, D, L, g.cs, B, probs,
-                       scoring ? &sc : nullptr);
-  return launch_status();
-}
 
-int run_backward(int32_t D, int32_t L, const float* const* params, const float* x, const int64_t* y,
-                 int32_t kind, float gscale, const float* gz, const float* gz_all, float* terms,
-                 float* grads, float* dx, int64_t B, void* ws, size_t ws_bytes, hipStream_t s,
-                 bool loss) {
-  Ptrs P;
-  Geo g;
-  Plan p;
-  int st = check_common(D, L, params, x, B, ws, ws_bytes, &P, &g, &p);
-  if (st != CNF_OK) return st;
-  if (!grads) return CNF_ERR_NULL;
-  if (loss) {
-    if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
-    if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
-    if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  static void fill(BwdArgs& a, const BwdCall&, float* tape) { a.tape = tape; }
+
+  static void finish(const Finish& f, const Ptrs&, int D, int L, const Geo& g, const BwdCall*,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, f.part, f.units, f.pw,
+                       f.nsum, f.sums, f.terms, f.grads, f.blob, D, L, g.dp, g.cs);
   }
-  if (mis4(gz) || mis4(gz_all) || mis4(grads) || mis4(dx)) return CNF_ERR_ALIGN;
-  const size_t gbytes = (size_t)L * (D + 2) * sizeof(float);
-  if (B == 0) {
-    st = hip_status(hipMemsetAsync(grads, 0, gbytes, s));
-    if (st == CNF_OK && loss) st = hip_status(hipMemsetAsync(terms, 0, 3 * sizeof(float), s));
-    return st;
-  }
-  float* w = static_cast<float*>(ws);
-  st = run_prep(P, g, D, L, w + p.blob, s);
-  if (st != CNF_OK) return st;
-  const int blocks = bwd_blocks(g, B);
-  const int units = bwd_units(g, B);
-  size_t lds = 0;
-  if (g.gacc) {
-    st = hip_status(hipMemsetAsync(w + p.part, 0, (size_t)units * g.pw * sizeof(float), s));
-    if (st != CNF_OK) return st;
-  } else {
-    lds = (size_t)kWaves * g.pw * sizeof(float);
-  }
-  BwdArgs a;
-  a.x = x;
-  a.blob = w + p.blob;
-  a.y = loss ? y : nullptr;
-  a.gz = loss ? nullptr : gz;
-  a.gz_all = loss ? nullptr : gz_all;
-  a.dx = dx;
-  a.part = w + p.part;
-  a.tape = w + p.tape;
-  a.B = B;
-  a.D = D;
-  a.L = L;
-  a.cs = g.cs;
-  a.ps = g.ps;
-  a.pw = g.pw;
-  a.gacc = g.gacc ? 1 : 0;
-  a.kind = kind;
-  a.gscale = gscale;
-  CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, s, a);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  hipLaunchKernelGGL(k_radial_finish, dim3(1), dim3(kFinThreads), 0, s, a.part, units, g.pw,
-                     L * g.ps, w + p.sums, loss ? terms : (float*)nullptr, grads, w + p.blob, D, L,
-                     g.dp, g.cs);
-  return launch_status();
-}
+};
 
 }  // namespace
 }  // namespace cnf
 
 extern "C" int cnf_radial_param_count(int32_t dim, int32_t n_layers, int64_t* n_floats) {
-  using namespace cnf;
-  if (!n_floats) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers);
-  if (st != CNF_OK) return st;
-  *n_floats = (int64_t)n_layers * (dim + 2);
-  return CNF_OK;
+  return cnf::rowflow::param_count(cnf::kFamily, cnf::Radial::grad_floats, dim, n_layers, n_floats);
 }
 
 extern "C" int cnf_radial_workspace_bytes(int32_t dim, int32_t n_layers, int64_t B,
@@ -825,8 +707,10 @@ extern "C" int cnf_radial_forward(int32_t dim, int32_t n_layers, const float* co
                                   const float* x, float* z, float* z_all, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_radial_forward");
-  return cnf::run_forward(dim, n_layers, params, x, nullptr, 0, z, z_all, nullptr, B, workspace,
-                          workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_forward<cnf::Radial>({dim, n_layers, params, x, nullptr, 0, 0.f, z,
+                                                 nullptr, z_all, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false,
+                                                 false});
 }
 
 extern "C" int cnf_radial_forward_loss(int32_t dim, int32_t n_layers, const float* const* params,
@@ -834,16 +718,19 @@ extern "C" int cnf_radial_forward_loss(int32_t dim, int32_t n_layers, const floa
                                        float* z, float* loss_terms, int64_t B, void* workspace,
                                        size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_radial_forward_loss");
-  return cnf::run_forward(dim, n_layers, params, x, y, loss_kind, z, nullptr, loss_terms, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, true);
+  return cnf::rowflow::run_forward<cnf::Radial>({dim, n_layers, params, x, y, loss_kind, 0.f, z,
+                                                 nullptr, nullptr, loss_terms, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true,
+                                                 false});
 }
 
 extern "C" int cnf_radial_predict(int32_t dim, int32_t n_layers, const float* const* params,
                                   const float* x, const float* log_priors, float* probs, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_radial_predict");
-  return cnf::run_predict(dim, n_layers, params, x, log_priors, probs, nullptr, 0, nullptr, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_predict<cnf::Radial>({dim, n_layers, params, x, log_priors, probs,
+                                                 nullptr, nullptr, 0, nullptr, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false});
 }
 
 extern "C" int cnf_radial_score(int32_t dim, int32_t n_layers, const float* const* params,
@@ -851,8 +738,9 @@ extern "C" int cnf_radial_score(int32_t dim, int32_t n_layers, const float* cons
                                 int32_t bins, int64_t* record, int64_t B, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_radial_score");
-  return cnf::run_predict(dim, n_layers, params, x, log_priors, nullptr, y, bins, record, B,
-                          workspace, workspace_bytes, (hipStream_t)stream, true);
+  return cnf::rowflow::run_predict<cnf::Radial>({dim, n_layers, params, x, log_priors, nullptr,
+                                                 nullptr, y, bins, record, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, true});
 }
 
 extern "C" int cnf_radial_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -860,8 +748,10 @@ extern "C" int cnf_radial_vjp(int32_t dim, int32_t n_layers, const float* const*
                               float* dx, int64_t B, void* workspace, size_t workspace_bytes,
                               void* stream) {
   CNF_RANGE("cnf_radial_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, nullptr, 0, 1.f, gz, gz_all, nullptr, grads,
-                           dx, B, workspace, workspace_bytes, (hipStream_t)stream, false);
+  return cnf::rowflow::run_backward<cnf::Radial>({dim, n_layers, params, x, nullptr, 0, 0.f, 1.f,
+                                                  gz, gz_all, nullptr, nullptr, grads, dx, B,
+                                                  workspace, workspace_bytes, (hipStream_t)stream,
+                                                  false});
 }
 
 extern "C" int cnf_radial_loss_vjp(int32_t dim, int32_t n_layers, const float* const* params,
@@ -870,7 +760,8 @@ extern "C" int cnf_radial_loss_vjp(int32_t dim, int32_t n_layers, const float* c
                                    int64_t B, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   CNF_RANGE("cnf_radial_loss_vjp");
-  return cnf::run_backward(dim, n_layers, params, x, y, loss_kind, grad_scale, nullptr, nullptr,
-                           loss_terms, grads, dx, B, workspace, workspace_bytes,
-                           (hipStream_t)stream, true);
+  return cnf::rowflow::run_backward<cnf::Radial>({dim, n_layers, params, x, y, loss_kind, 0.f,
+                                                  grad_scale, nullptr, nullptr, nullptr, loss_terms,
+                                                  grads, dx, B, workspace, workspace_bytes,
+                                                  (hipStream_t)stream, true});
 }

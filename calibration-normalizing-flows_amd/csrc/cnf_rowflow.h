@@ -1,17 +1,24 @@
 // What the row-wise flow families (cnf_planar.hip, cnf_radial.hip,
 // cnf_affine.hip) share: the grid constants, the geometry of a row in lanes, the
-// workspace plan, the argument checks, the shape dispatch and the lane helpers.
+// workspace plan, the shape dispatch, the lane helpers, and the whole host layer
+// between the extern "C" entry points and the launches: the argument checks
+// and their order, the B == 0 contract, the prep launch, the choice between
+// workspace and LDS records, the finish launch and the status tail
+// (run_forward, run_predict, run_backward).
 // A family differs from the others in three geometry words -- cs, the floats of
 // its per-layer constant record, ps, the row sums per layer of its reverse
 // mode, and tf, the tape floats per (row, layer) its deep stacks keep in the
 // workspace (1, or 0 for a family without such a tape) -- which it passes to
-// geometry(), and in its parameter tensors per layer (RowFamily::tensors).
+// geometry(), in its parameter tensors per layer (RowFamily::tensors), and in
+// what its policy type says (below, "the launch layer"): its kernels'
+// argument lists and the gradient floats of a layer.
 //
 // Everything here is either host code or an inline device function that was
 // one already; the kernel bodies stay in their files, because wrapping kernel
 // text in a helper makes the compiler schedule it differently.
-// `Ptrs`, the by-value pointer table of the prep and finish kernels, stays in
-// each file too: its namespace is part of those kernels' names.
+// `Ptrs`, the by-value pointer table of the prep and finish kernels, and
+// `BwdArgs` stay in each file too: their namespace is part of those kernels'
+// names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +26,7 @@
 #include <cstdint>
 
 #include "cnf_internal.h"
+#include "cnf_score.h"
 
 namespace cnf {
 namespace rowflow {
@@ -197,7 +205,7 @@ inline int check_shape(int32_t dim, int32_t n_layers, int max_layers) {
 // Which instantiation of a family's reverse-mode kernel a launch takes: regt,
 // the tape in registers (L <= kRegL); rega, per-lane accumulators on top of it
 // (the family says for which geometries).  One helper per family answers it,
-// for launch_bwd and for cnf_<family>_launch_plan alike.
+// for its policy's bwd launcher and for cnf_<family>_launch_plan alike.
 struct BwdVariant {
   bool regt, rega;
 };
@@ -265,6 +273,209 @@ inline int launch_plan(const RowFamily& f, int32_t dim, int32_t n_layers, int64_
   out[6] = bwd_blocks(g, B);
   out[7] = bwd_units(g, B);
   return CNF_OK;
+}
+
+// the body of cnf_<family>_param_count
+static inline int param_count(const RowFamily& f, int (*grad_floats)(int D), int32_t dim,
+                              int32_t n_layers, int64_t* n_floats) {
+  if (!n_floats) return CNF_ERR_NULL;
+  const int st = check_shape(dim, n_layers, f.max_layers);
+  if (st != CNF_OK) return st;
+  *n_floats = (int64_t)n_layers * grad_floats(dim);
+  return CNF_OK;
+}
+
+// ---- the launch layer -------------------------------------------------------------
+//
+// One record per kind of call, with every argument any family has; an entry
+// point whose family lacks one passes null / 0 (mis4(nullptr) is false, so one
+// alignment line serves all).  run_forward, run_predict and run_backward own
+// the order of the checks, which is part of the ABI (DESIGN.md 7k states it).
+// A family's policy type F, defined in its file's anonymous namespace, supplies
+//   Table, Args             its Ptrs and BwdArgs
+//   family()                its RowFamily
+//   grad_floats(D)          gradient (= parameter) floats per layer
+//   kLdScalar               whether the log-det is one number [1], not a row's [B]
+//   prep(P, g, D, L, blob, inv, s)                 the constant-record launch
+//   fwd / predict / bwd <LPR, CPL>(...)            its kernels' launches
+//   fill(a, call, tape)     the words of Args only this family has
+//   finish(f, P, D, L, g, call, s)                 the one-block reduction's launch
+
+struct FwdCall {
+  int32_t D, L;
+  const float* const* params;
+  const float* x;
+  const int64_t* y;  // null unless loss
+  int32_t kind;
+  float det;
+  float *z, *ld, *z_all, *terms;
+  int64_t B;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+  bool loss, inv;
+};
+
+struct PredictCall {
+  int32_t D, L;
+  const float* const* params;
+  const float *x, *lp;
+  float *probs, *ld;
+  const int64_t* y;  // scoring: labels, bins, record
+  int32_t bins;
+  int64_t* record;
+  int64_t B;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+  bool scoring;
+};
+
+struct BwdCall {
+  int32_t D, L;
+  const float* const* params;
+  const float* x;
+  const int64_t* y;
+  int32_t kind;
+  float det, gscale;
+  const float *gz, *gz_all, *gld;
+  float *terms, *grads, *dx;
+  int64_t B;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+  bool loss;
+};
+
+// What a finish launch adds up: `units` records of `pw` words at `part`, the
+// first `nsum` of them row sums (to `sums`), the next three the loss terms.
+struct Finish {
+  const float* part;
+  int units, pw, nsum;
+  float *sums, *terms, *grads;
+  const float* blob;
+};
+
+static inline int check_loss(int32_t kind, const int64_t* y, const float* terms, int64_t B) {
+  if (kind != CNF_LOSS_CAL && kind != CNF_LOSS_CE) return CNF_ERR_DESC;
+  if (!terms || (B > 0 && !y)) return CNF_ERR_NULL;
+  if (mis8(y) || mis4(terms)) return CNF_ERR_ALIGN;
+  return CNF_OK;
+}
+
+static inline int zero_floats(float* p, size_t n, hipStream_t s) {
+  return hip_status(hipMemsetAsync(p, 0, n * sizeof(float), s));
+}
+
+// forward, forward + loss (c.loss), inverse (c.inv)
+template <class F>
+int run_forward(const FwdCall& c) {
+  typename F::Table P;
+  Geo g;
+  Plan p;
+  int st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  if (st != CNF_OK) return st;
+  if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
+  if (mis4(c.z) || mis4(c.ld) || mis4(c.z_all)) return CNF_ERR_ALIGN;
+  if (c.B == 0) {  // no row: the terms are 0; a [1] log-det is not formed without a launch
+    if (c.loss) st = zero_floats(c.terms, 3, c.s);
+    if (st == CNF_OK && F::kLdScalar && c.ld) st = zero_floats(c.ld, 1, c.s);
+    return st;
+  }
+  float* w = static_cast<float*>(c.ws);
+  F::prep(P, g, c.D, c.L, w + p.blob, c.inv, c.s);
+  st = launch_status();
+  if (st != CNF_OK) return st;
+  const int blocks = fwd_blocks(g, c.B);
+  float* part = c.loss ? w + p.part : nullptr;
+  CNF_ROWFLOW_DISPATCH(F::template fwd, blocks, c, g, w + p.blob, part);
+  st = launch_status();
+  if (st != CNF_OK || !c.loss) return st;
+  F::finish(Finish{part, blocks, 4, 0, w + p.sums, c.terms, nullptr, w + p.blob}, P, c.D, c.L, g,
+            nullptr, c.s);
+  return launch_status();
+}
+
+// predict, or score (c.scoring)
+template <class F>
+int run_predict(const PredictCall& c) {
+  typename F::Table P;
+  Geo g;
+  Plan p;
+  int st = check_shape(c.D, c.L, F::family().max_layers);
+  if (st != CNF_OK) return st;
+  if (c.scoring && (st = score::check_args(c.D, c.bins, c.B, c.y, c.record)) != CNF_OK) return st;
+  st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  if (st != CNF_OK) return st;
+  if (c.B > 0 && (!c.lp || (!c.scoring && !c.probs))) return CNF_ERR_NULL;
+  if (mis4(c.lp) || mis4(c.probs) || mis4(c.ld)) return CNF_ERR_ALIGN;
+  if (c.B == 0) return CNF_OK;
+  float* w = static_cast<float*>(c.ws);
+  F::prep(P, g, c.D, c.L, w + p.blob, false, c.s);
+  st = launch_status();
+  if (st != CNF_OK) return st;
+  score::Args sc;
+  if (c.scoring) sc = score::make_args(c.y, c.bins, c.record);
+  CNF_ROWFLOW_DISPATCH(F::template predict, fwd_blocks(g, c.B), c, g, w + p.blob,
+                       c.scoring ? &sc : nullptr);
+  return launch_status();
+}
+
+// reverse mode from upstream gradients, or fused with the loss (c.loss)
+template <class F>
+int run_backward(const BwdCall& c) {
+  typename F::Table P;
+  Geo g;
+  Plan p;
+  int st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  if (st != CNF_OK) return st;
+  if (!c.grads) return CNF_ERR_NULL;
+  if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
+  if (mis4(c.gz) || mis4(c.gz_all) || mis4(c.gld) || mis4(c.grads) || mis4(c.dx))
+    return CNF_ERR_ALIGN;
+  if (c.B == 0) {
+    st = zero_floats(c.grads, (size_t)c.L * F::grad_floats(c.D), c.s);
+    if (st == CNF_OK && c.loss) st = zero_floats(c.terms, 3, c.s);
+    return st;
+  }
+  float* w = static_cast<float*>(c.ws);
+  F::prep(P, g, c.D, c.L, w + p.blob, false, c.s);
+  st = launch_status();
+  if (st != CNF_OK) return st;
+  const int blocks = bwd_blocks(g, c.B);
+  const int units = bwd_units(g, c.B);
+  size_t lds = 0;
+  if (g.gacc) {
+    st = zero_floats(w + p.part, (size_t)units * g.pw, c.s);
+    if (st != CNF_OK) return st;
+  } else {
+    lds = (size_t)kWaves * g.pw * sizeof(float);
+  }
+  typename F::Args a;  // the words every family's BwdArgs has, then its own
+  a.x = c.x;
+  a.blob = w + p.blob;
+  a.y = c.loss ? c.y : nullptr;
+  a.gz = c.loss ? nullptr : c.gz;
+  a.gz_all = c.loss ? nullptr : c.gz_all;
+  a.dx = c.dx;
+  a.part = w + p.part;
+  a.B = c.B;
+  a.D = c.D;
+  a.L = c.L;
+  a.cs = g.cs;
+  a.ps = g.ps;
+  a.pw = g.pw;
+  a.gacc = g.gacc ? 1 : 0;
+  a.kind = c.kind;
+  a.gscale = c.gscale;
+  F::fill(a, c, w + p.tape);
+  CNF_ROWFLOW_DISPATCH(F::template bwd, blocks, lds, c.s, a);
+  st = launch_status();
+  if (st != CNF_OK) return st;
+  F::finish(Finish{a.part, units, g.pw, c.L * g.ps, w + p.sums, c.loss ? c.terms : nullptr, c.grads,
+                   w + p.blob},
+            P, c.D, c.L, g, &c, c.s);
+  return launch_status();
 }
 
 }  // namespace rowflow

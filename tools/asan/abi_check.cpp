@@ -10,7 +10,8 @@
 // unknown option bits -- each through every size query and every launching
 // entry point with a rejected argument (negative batch, NULL blob), so ASan
 // sees the validation code read exactly the caller's arrays: the permutation
-// table is a heap block of exactly L*D int64s.
+// table is a heap block of exactly L*D int64s.  The row families' argument
+// paths (cnf_rowflow.h's launch layer) follow the same pattern, below.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -31,6 +32,197 @@ static int g_fail = 0;
   } while (0)
 
 static bool is_status(int st) { return st <= 0 && st >= -6; }
+
+// ---- the row families (cnf_planar_*, cnf_radial_*, cnf_affine_*) ------------------
+//
+// Their common checks copy the caller's parameter table into a tensors *
+// max_layers pointer table on the entry point's stack.  The table handed in
+// is a heap block of exactly tensors * L pointers (one pointer when the shape
+// is out of range and nothing may be read), so ASan sees both ends.  Every
+// launching call carries exactly one fault that returns before any HIP call;
+// the pointers are fake and never followed on the host.
+
+struct RowArgs {
+  int32_t dim, L;
+  const float* const* params;
+  const float* x;
+  int64_t B;
+  void* ws;
+  size_t wb;
+  int32_t kind, bins;
+  float* grads;
+};
+
+enum { ROW_LOSS = 1, ROW_BWD = 2, ROW_SCORE = 4 };
+struct RowEntry {
+  int cat;
+  int (*fn)(const RowArgs&);
+};
+struct RowFamilyAbi {
+  int tensors, max_layers;
+  int (*grad_floats)(int D);
+  int (*param_count)(int32_t, int32_t, int64_t*);
+  int (*workspace_bytes)(int32_t, int32_t, int64_t, size_t*);
+  int (*launch_plan)(int32_t, int32_t, int64_t, int32_t*);
+  std::vector<RowEntry> entries;
+};
+
+alignas(8) static float g_f[8];
+alignas(8) static int64_t g_i[8];
+
+static const RowFamilyAbi kPlanar = {
+    3, CNF_PLANAR_MAX_LAYERS, [](int D) { return 2 * D + 1; }, cnf_planar_param_count,
+    cnf_planar_workspace_bytes, cnf_planar_launch_plan,
+    {{0, [](const RowArgs& a) {
+        return cnf_planar_forward(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_LOSS, [](const RowArgs& a) {
+        return cnf_planar_forward_loss(a.dim, a.L, a.params, a.x, g_i, a.kind, 1.f, g_f, g_f, g_f,
+                                       a.B, a.ws, a.wb, nullptr);
+      }},
+     {0, [](const RowArgs& a) {
+        return cnf_planar_predict(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_SCORE, [](const RowArgs& a) {
+        return cnf_planar_score(a.dim, a.L, a.params, a.x, g_f, g_i, a.bins, g_i, a.B, a.ws, a.wb,
+                                nullptr);
+      }},
+     {ROW_BWD, [](const RowArgs& a) {
+        return cnf_planar_vjp(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.grads, g_f, a.B, a.ws, a.wb,
+                              nullptr);
+      }},
+     {ROW_BWD | ROW_LOSS, [](const RowArgs& a) {
+        return cnf_planar_loss_vjp(a.dim, a.L, a.params, a.x, g_i, a.kind, 1.f, 1.f, g_f, a.grads,
+                                   g_f, a.B, a.ws, a.wb, nullptr);
+      }}}};
+
+static const RowFamilyAbi kRadial = {
+    3, CNF_RADIAL_MAX_LAYERS, [](int D) { return D + 2; }, cnf_radial_param_count,
+    cnf_radial_workspace_bytes, cnf_radial_launch_plan,
+    {{0, [](const RowArgs& a) {
+        return cnf_radial_forward(a.dim, a.L, a.params, a.x, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_LOSS, [](const RowArgs& a) {
+        return cnf_radial_forward_loss(a.dim, a.L, a.params, a.x, g_i, a.kind, g_f, g_f, a.B, a.ws,
+                                       a.wb, nullptr);
+      }},
+     {0, [](const RowArgs& a) {
+        return cnf_radial_predict(a.dim, a.L, a.params, a.x, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_SCORE, [](const RowArgs& a) {
+        return cnf_radial_score(a.dim, a.L, a.params, a.x, g_f, g_i, a.bins, g_i, a.B, a.ws, a.wb,
+                                nullptr);
+      }},
+     {ROW_BWD, [](const RowArgs& a) {
+        return cnf_radial_vjp(a.dim, a.L, a.params, a.x, g_f, g_f, a.grads, g_f, a.B, a.ws, a.wb,
+                              nullptr);
+      }},
+     {ROW_BWD | ROW_LOSS, [](const RowArgs& a) {
+        return cnf_radial_loss_vjp(a.dim, a.L, a.params, a.x, g_i, a.kind, 1.f, g_f, a.grads, g_f,
+                                   a.B, a.ws, a.wb, nullptr);
+      }}}};
+
+static const RowFamilyAbi kAffine = {
+    2, CNF_AFFINE_MAX_LAYERS, [](int D) { return 2 * D; }, cnf_affine_param_count,
+    cnf_affine_workspace_bytes, cnf_affine_launch_plan,
+    {{0, [](const RowArgs& a) {
+        return cnf_affine_forward(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {0, [](const RowArgs& a) {
+        return cnf_affine_inverse(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_LOSS, [](const RowArgs& a) {
+        return cnf_affine_forward_loss(a.dim, a.L, a.params, a.x, g_i, a.kind, 1.f, g_f, g_f, g_f,
+                                       a.B, a.ws, a.wb, nullptr);
+      }},
+     {0, [](const RowArgs& a) {
+        return cnf_affine_predict(a.dim, a.L, a.params, a.x, g_f, g_f, a.B, a.ws, a.wb, nullptr);
+      }},
+     {ROW_SCORE, [](const RowArgs& a) {
+        return cnf_affine_score(a.dim, a.L, a.params, a.x, g_f, g_i, a.bins, g_i, a.B, a.ws, a.wb,
+                                nullptr);
+      }},
+     {ROW_BWD, [](const RowArgs& a) {
+        return cnf_affine_vjp(a.dim, a.L, a.params, a.x, g_f, g_f, g_f, a.grads, g_f, a.B, a.ws, a.wb,
+                              nullptr);
+      }},
+     {ROW_BWD | ROW_LOSS, [](const RowArgs& a) {
+        return cnf_affine_loss_vjp(a.dim, a.L, a.params, a.x, g_i, a.kind, 1.f, 1.f, g_f, a.grads,
+                                   g_f, a.B, a.ws, a.wb, nullptr);
+      }}}};
+
+// One seeded (dim, L, B), the three host queries, then every launching entry
+// point once per fault.  `want` is the fault's own status; a shape or batch
+// outside the envelope is rejected first, with a status of its own.
+template <class Rng>
+static void row_family_check(const RowFamilyAbi& f, Rng& rng) {
+  auto U = [&](int lo, int hi) { return (int)std::uniform_int_distribution<int>(lo, hi)(rng); };
+  const int32_t dim = U(0, 9) == 0 ? U(-3, 300) : U(1, CNF_MAX_DIM);
+  const int32_t L = U(0, 5) == 0 ? f.max_layers : U(0, 9) == 0 ? U(-2, f.max_layers + 6) : U(1, 12);
+  const int64_t B = U(0, 5) != 0 ? (int64_t)U(1, 1 << 20)
+                    : U(0, 1)    ? -(int64_t)U(1, 9)
+                                 : ((int64_t)1 << 31) + U(1, 9);
+  const bool shape_ok = dim >= 1 && dim <= CNF_MAX_DIM && L >= 1 && L <= f.max_layers;
+  const bool ok = shape_ok && B >= 0 && B <= ((int64_t)1 << 31);
+  int64_t nf = -1;
+  size_t need = 0;
+  int32_t plan[8] = {0};
+  const int sp = f.param_count(dim, L, &nf);
+  EXPECT(is_status(sp) && (sp == CNF_OK) == shape_ok);
+  if (shape_ok) EXPECT(nf == (int64_t)L * f.grad_floats(dim));
+  const int sw = f.workspace_bytes(dim, L, B, &need);
+  EXPECT(is_status(sw) && (sw == CNF_OK) == ok);
+  const int sl = f.launch_plan(dim, L, B, plan);
+  EXPECT(is_status(sl) && (sl == CNF_OK) == ok);
+  if (ok) EXPECT(need > 0 && need % 256 == 0 && plan[0] * plan[1] >= dim && plan[5] >= 1);
+  EXPECT(f.param_count(dim, L, nullptr) == CNF_ERR_NULL);
+  EXPECT(f.workspace_bytes(dim, L, B, nullptr) == CNF_ERR_NULL);
+  EXPECT(f.launch_plan(dim, L, B, nullptr) == CNF_ERR_NULL);
+
+  const int n = shape_ok ? f.tensors * L : 1;
+  auto table = [&] {  // fresh, of exactly n fake aligned pointers
+    std::vector<const float*> t(n);
+    for (int i = 0; i < n; ++i) t[i] = reinterpret_cast<const float*>((uintptr_t)4096 + 64 * i);
+    return t;
+  };
+  const RowArgs good = {dim, L, nullptr, g_f, B, g_f, need, CNF_LOSS_CAL, 15, g_f};
+  // cats: the entry points the fault reaches (0: all); score's own checks come
+  // before the common ones, so it may answer a common fault with its batch cap
+  auto run = [&](RowArgs a, const std::vector<const float*>* t, int cats, int want) {
+    a.params = t ? t->data() : nullptr;
+    for (const RowEntry& e : f.entries) {
+      if (cats && !(e.cat & cats)) continue;
+      const int st = e.fn(a);
+      EXPECT(st < 0 && is_status(st));
+      const bool capped = (e.cat & ROW_SCORE) && (dim < 2 || B > (1 << 26));
+      if (ok && !capped) EXPECT(st == want);
+    }
+  };
+  std::vector<const float*> t = table();
+  run(good, nullptr, 0, CNF_ERR_NULL);                       // a null table
+  const int at = U(0, 2) == 0 ? n - 1 : U(0, n - 1);         // ... entry, the last one included
+  t[at] = nullptr;
+  run(good, &t, 0, CNF_ERR_NULL);
+  t = table();
+  t[at] = reinterpret_cast<const float*>((uintptr_t)4098);
+  run(good, &t, 0, CNF_ERR_ALIGN);
+  t = table();
+  RowArgs a = good;
+  a.wb = need - 4;                                           // a short workspace
+  run(a, &t, 0, CNF_ERR_NULL);
+  a = good;
+  a.x = reinterpret_cast<const float*>((const char*)g_f + 2);
+  run(a, &t, 0, CNF_ERR_ALIGN);
+  a = good;
+  a.kind = U(2, 9);
+  run(a, &t, ROW_LOSS, CNF_ERR_DESC);
+  a = good;
+  a.grads = nullptr;
+  run(a, &t, ROW_BWD, CNF_ERR_NULL);
+  a = good;
+  a.bins = U(0, 1) ? -U(0, 3) : CNF_MAX_BINS + U(1, 9);
+  run(a, &t, ROW_SCORE, CNF_ERR_DESC);
+}
 
 int main(int argc, char** argv) {
   const int iters = argc > 1 ? std::atoi(argv[1]) : 3000;
@@ -186,6 +378,7 @@ int main(int argc, char** argv) {
       for (int k = 0; k < 4; ++k) EXPECT(tx[k] == 7 && ty[k] == 7 && nt[k] == 7 && out[k] == 7);
     }
     delete perms;
+    for (const RowFamilyAbi* f : {&kPlanar, &kRadial, &kAffine}) row_family_check(*f, rng);
   }
   EXPECT(cnf_param_count(nullptr, nullptr) == CNF_ERR_NULL);
   EXPECT(n_ok > iters / 10);
