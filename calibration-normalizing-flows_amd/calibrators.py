@@ -463,10 +463,10 @@ def _native_stack(flow, dev, need_vjp=True):
 
 
 def _tensor_stack(flow, dev):
-    """The fused PlanarStack, RadialStack or AffineStack behind `flow` (the
-    stacks without a cnf_desc, whose parameters StackAdam steps as a tensor
-    list), or None when the flow is not an all-planar, all-radial or all-affine
-    Flow with fp32 parameters on the ROCm device `dev` (an affine layer needs
+    """The fused PlanarStack, RadialStack, AffineStack or MixedStack behind `flow`
+    (the stacks without a cnf_desc, whose parameters StackAdam steps as a tensor
+    list), or None when the flow is not an all-planar, all-radial, all-affine or
+    mixed planar/radial/affine Flow with fp32 parameters on the ROCm device `dev` (an affine layer needs
     both of its parameters), the shape is outside the kernels' envelope, or the
     family's switch (CNF_PLANAR_NATIVE=0 / CNF_RADIAL_NATIVE=0 /
     CNF_AFFINE_NATIVE=0) is off."""
@@ -496,7 +496,32 @@ def _tensor_stack(flow, dev):
         if not (1 <= ps[0].numel() <= _lib.MAX_DIM and len(layers) <= max_layers):
             continue
         return flow._row_stack(cls, layers)
-    return None
+    return _mixed_stack(flow, F, _lib)
+
+
+def _mixed_stack(flow, F, _lib):
+    """The fused MixedStack behind a Flow that mixes planar, radial and affine
+    layers of one width (parameters fp32 on the ROCm device), or None: as
+    flows._mixed_class decides per call, here for any batch of two or more
+    rows, which is what a fit, a predict and a score run on."""
+    if not isinstance(flow, F.Flow) or not F.MIXED_NATIVE:
+        return None
+    layers = list(flow.layers)
+    families = {getattr(l, "_family", None) for l in layers}
+    switches = F._family_switches()
+    if len(families) < 2 or not all(switches.get(f, False) for f in families):
+        return None
+    if layers[0]._family == "radial" or F.mixed_logdet_shape(layers, 2) is None:
+        return None
+    from cnf_hip.mixed import MixedStack
+    ps = [p for l in layers for p in MixedStack.layer_tensors(l)]
+    if not all(isinstance(p, nn.Parameter) and p.is_cuda for p in ps):
+        return None
+    if not MixedStack.compatible(layers, ps[0].device):
+        return None
+    if not (1 <= ps[0].numel() <= _lib.MAX_DIM and len(layers) <= _lib.MIXED_MAX_LAYERS):
+        return None
+    return flow._row_stack(MixedStack, layers)
 
 
 def _history(terms_all, epochs, N):

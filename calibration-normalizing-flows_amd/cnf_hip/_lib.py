@@ -35,6 +35,10 @@ PLANAR_REG_LAYERS = 10  # deeper stacks keep their tanh tape in the workspace
 RADIAL_MAX_LAYERS = 64  # CNF_RADIAL_MAX_LAYERS (cnf_radial_*)
 RADIAL_REG_LAYERS = 10  # deeper stacks keep their tape of r in the workspace
 AFFINE_MAX_LAYERS = 64  # CNF_AFFINE_MAX_LAYERS (cnf_affine_*)
+MIXED_MAX_LAYERS = 64   # CNF_MIXED_MAX_LAYERS (cnf_mixed_*)
+LAYER_PLANAR = 0        # CNF_LAYER_*: a mixed stack's `kinds`
+LAYER_RADIAL = 1
+LAYER_AFFINE = 2
 VJP_PLAN_WORDS = 16     # CNF_VJP_PLAN_WORDS (cnf_vjp_launch_plan)
 VJP_PATHS = ("none", "vjp2", "vjp-rows", "layerwise", "wide-fused")  # CNF_VJP_PATH_*
 # k_wgemm's instantiations in cnf_vjp_launch_plan's bit order: (BT, EPI, PAIR, NC)
@@ -69,6 +73,9 @@ EXPORTS = (
     "cnf_affine_forward", "cnf_affine_inverse",
     "cnf_affine_forward_loss", "cnf_affine_predict", "cnf_affine_score", "cnf_affine_vjp",
     "cnf_affine_loss_vjp",
+    "cnf_mixed_param_count", "cnf_mixed_workspace_bytes", "cnf_mixed_launch_plan",
+    "cnf_mixed_forward", "cnf_mixed_forward_loss", "cnf_mixed_predict", "cnf_mixed_score",
+    "cnf_mixed_vjp", "cnf_mixed_loss_vjp",
     "cnf_kernel_name", "cnf_vjp_kernel_name", "cnf_vjp_launch_plan", "cnf_strerror", "cnf_last_hip_error", "cnf_abi_version",
 )
 
@@ -199,6 +206,26 @@ def _bind(lib):
                                           ctypes.c_size_t, P]),
         "cnf_affine_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(P), P, P, I32, F, F, P, P,
                                                P, I64, P, ctypes.c_size_t, P]),
+        # the planar signatures with `kinds` (a host int32 array) after n_layers
+        "cnf_mixed_param_count": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32),
+                                                 ctypes.POINTER(I64)]),
+        "cnf_mixed_workspace_bytes": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), I64,
+                                                     ctypes.POINTER(ctypes.c_size_t)]),
+        "cnf_mixed_launch_plan": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), I64,
+                                                 ctypes.POINTER(I32)]),
+        "cnf_mixed_forward": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(P), P,
+                                             P, P, P, I64, P, ctypes.c_size_t, P]),
+        "cnf_mixed_forward_loss": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32),
+                                                  ctypes.POINTER(P), P, P, I32, F, P, P, P, I64,
+                                                  P, ctypes.c_size_t, P]),
+        "cnf_mixed_predict": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(P), P,
+                                             P, P, P, I64, P, ctypes.c_size_t, P]),
+        "cnf_mixed_score": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(P), P, P,
+                                           P, I32, P, I64, P, ctypes.c_size_t, P]),
+        "cnf_mixed_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(P), P, P,
+                                         P, P, P, P, I64, P, ctypes.c_size_t, P]),
+        "cnf_mixed_loss_vjp": (ctypes.c_int, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(P), P,
+                                              P, I32, F, F, P, P, P, I64, P, ctypes.c_size_t, P]),
         "cnf_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_vjp_kernel_name": (ctypes.c_char_p, [D]),
         "cnf_vjp_launch_plan": (ctypes.c_int, [D, I64, I32, ctypes.POINTER(I32)]),

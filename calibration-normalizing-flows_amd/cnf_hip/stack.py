@@ -8,7 +8,8 @@ keep owning their parameters; the stack lists them once in ABI order
 (`_params`).  Buffers are torch allocations on the input's device and the
 launches go to torch's current stream there.  A subclass sets
 
-  family      "coupling" / "planar" / "radial" / "affine": the word in the error texts
+  family      "coupling" / "planar" / "radial" / "affine" / "mixed": the word in the
+              error texts
   _rows       what the input check calls its rows
   _fp32_why   why the path is fp32, in the dtype error
   _stale      what a stale backward says changed
@@ -28,7 +29,9 @@ stats = {"forward": 0, "inverse": 0, "prepare": 0, "vjp": 0, "loss_vjp": 0, "pre
          "radial_forward": 0, "radial_vjp": 0, "radial_loss_vjp": 0, "radial_predict": 0,
          "radial_score": 0,
          "affine_forward": 0, "affine_inverse": 0, "affine_vjp": 0, "affine_loss_vjp": 0,
-         "affine_predict": 0, "affine_score": 0}
+         "affine_predict": 0, "affine_score": 0,
+         "mixed_forward": 0, "mixed_vjp": 0, "mixed_loss_vjp": 0, "mixed_predict": 0,
+         "mixed_score": 0}
 
 
 def _ptr(t):

@@ -94,3 +94,31 @@ class AffineConstantFlow(Flow):
     def forward_all(self, x):
         """The reference Flow.forward: (zs list, cum_log_det)."""
         return Flow.forward(self, x)
+
+
+class MixedFlow(Flow):
+    """A Flow that mixes the three row-wise layers, whose call returns
+    (z_final, log_det): `layers` is a spec string over P (PlanarLayer), R
+    (RadialLayer) and A (AffineConstantLayer), one letter per layer in order,
+    e.g. "PRPRA".  On a ROCm device one fused launch per call (cnf_mixed_*)
+    for every order whose log-det the layer loop accepts: planar first for a
+    batch of more than one row (flows.mixed_logdet_shape).  The default is
+    unpinned (no notebook builds one)."""
+
+    _LAYERS = {"P": PlanarLayer, "R": RadialLayer, "A": AffineConstantLayer}
+
+    def __init__(self, dim, layers="PRPRA", **kwargs):
+        spec = str(layers).upper()
+        if not spec or any(c not in self._LAYERS for c in spec):
+            raise ValueError("MixedFlow: layers must be a non-empty string over P, R, A; got %r"
+                             % (layers,))
+        super().__init__([self._LAYERS[c](dim) for c in spec])
+        self.dim = dim
+        self.spec = spec
+
+    def forward(self, x):
+        return self.transform(x)
+
+    def forward_all(self, x):
+        """The reference Flow.forward: (zs list, cum_log_det)."""
+        return Flow.forward(self, x)

@@ -19,10 +19,14 @@ inverse, the log-det one number of shape [1] as the reference's):
 from torch autograd, which calls the native VJP kernel.
 
 Host tensors (CPU) run the same math with torch ops, as the reference does.
+A Flow that mixes PlanarLayers, RadialLayers and AffineConstantLayers of one
+width runs as one fused launch too (cnf_mixed_*), whenever the layer loop
+would accept its order (mixed_logdet_shape).
 Layers the native engine does not cover (an AffineConstantLayer built with
-scale=False or shift=False) and mixed stacks run as torch ops, layer by layer,
-and so does Flow.backward of an affine flow under autograd (the native inverse
-has no reverse mode).  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops
+scale=False or shift=False) and stacks that mix them or coupling layers in run
+layer by layer, and so does Flow.backward of an affine flow under autograd
+(the native inverse has no reverse mode).  CNF_MIXED_NATIVE=0 keeps mixed
+flows on that loop.  CNF_PLANAR_NATIVE=0 keeps planar flows on the torch ops
 as well, CNF_RADIAL_NATIVE=0 radial ones and CNF_AFFINE_NATIVE=0 affine ones.  A radial stack's log-det is the reference's
 constant log(1) = 0: the native path returns the same 0-d fp32 zero.
 
@@ -62,6 +66,10 @@ RADIAL_NATIVE = os.environ.get("CNF_RADIAL_NATIVE", "1") != "0"
 # CNF_AFFINE_NATIVE=0: the same for affine-constant flows (the baseline of
 # tools/affine_bench.py).
 AFFINE_NATIVE = os.environ.get("CNF_AFFINE_NATIVE", "1") != "0"
+# CNF_MIXED_NATIVE=0: flows that mix planar, radial and affine layers run layer
+# by layer, each layer on its own family's launch (the baseline of
+# tools/mixed_bench.py).
+MIXED_NATIVE = os.environ.get("CNF_MIXED_NATIVE", "1") != "0"
 
 _warned = set()
 
@@ -105,14 +113,58 @@ def _native_eligible(layers, x):
     return True
 
 
+def _family_switches():
+    return {"planar": PLANAR_NATIVE, "radial": RADIAL_NATIVE, "affine": AFFINE_NATIVE}
+
+
+def mixed_logdet_shape(layers, B):
+    """The shape of the log-det the layer loop of Flow.forward gives a flow of
+    planar, radial and affine layers on B rows, or None when the loop raises.
+    The loop accumulates in place into the first layer's log-det, so that
+    shape must already be the broadcast of every layer's: planar [B] (0-d for
+    one row, after its squeeze), radial 0-d, affine [1]."""
+    per = {"planar": () if B == 1 else (B,), "radial": (), "affine": (1,)}
+    shapes = {per[ly._family] for ly in layers}
+    # the broadcast of 0-d, [1] and [B] shapes: the rows' where there is one
+    # ([0] for no row), else [1] where there is one, else 0-d
+    full = (B,) if (B,) in shapes else (1,) if (1,) in shapes else ()
+    first = per[layers[0]._family]
+    return first if full == first else None
+
+
+def _mixed_class(layers, x, families):
+    """MixedStack when these layers -- planar, radial and affine, at least two
+    of the classes -- can run on x as one fused launch, or None: every layer
+    compatible on its own (an affine layer with both parameters, every tensor
+    on x's device), one width, no switch of a family present turned off, and an
+    order whose log-det the layer loop accepts on x's rows
+    (mixed_logdet_shape).  A radial first layer stays on the loop: its log-det
+    is a host tensor, into which the loop cannot accumulate a device one."""
+    switches = _family_switches()
+    if not MIXED_NATIVE or not all(switches.get(f, False) for f in families):
+        return None
+    if not _device_rows(x) or layers[0]._family == "radial":
+        return None
+    shape = mixed_logdet_shape(layers, x.shape[0])
+    if shape is None or (shape == (1,) and x.shape[0] == 0):  # [1] of no row: the loop's ops
+        return None
+    from cnf_hip.mixed import MixedStack
+    if not MixedStack.compatible(layers, x.device):
+        return None
+    return MixedStack if x.shape[1] == MixedStack.layer_tensors(layers[0])[0].numel() else None
+
+
 def _row_class(layers, x):
-    """The stack class (PlanarStack / RadialStack / AffineStack) under which these layers can
+    """The stack class (PlanarStack / RadialStack / AffineStack, or MixedStack for
+    layers of more than one of their classes) under which these layers can
     run on x as one fused launch of a row-wise family, or None.  The family's
     switch is read here, at call time, and with the input's device before
     anything of cnf_hip is touched."""
+    families = {getattr(ly, "_family", None) for ly in layers}
+    if len(families) > 1:
+        return None if None in families else _mixed_class(layers, x, families)
     family = getattr(layers[0], "_family", None) if layers else None
-    if family is None or not {"planar": PLANAR_NATIVE, "radial": RADIAL_NATIVE,
-                              "affine": AFFINE_NATIVE}[family]:
+    if family is None or not _family_switches()[family]:
         return None
     if not _device_rows(x):
         return None
@@ -148,6 +200,12 @@ def _run_stack(stack, x, want_all, inverse=False):
             out = allt if want_all else fin
         if stack.squeeze_logdet:
             ld = _squeeze_ld(ld)
+        elif stack.family == "mixed":
+            # the loop's shape: the rows' [B], or the first row of [B] rows that
+            # agree ([1], 0-d) -- a slice, so autograd reaches the kernel's gld
+            shape = mixed_logdet_shape(stack.layers, x.shape[0])
+            if shape != tuple(ld.shape):
+                ld = ld[:1].reshape(shape)
         return (list(out.unbind(0)) if want_all else out), ld
     except UnsupportedShape as e:
         _not_native(str(e))
@@ -194,8 +252,9 @@ class Flow(nn.Module):
         self._drop_bindings(self.__dict__)
 
     # the lazily built native bindings, each with the key it was built for:
-    # the CouplingStack, the PlanarStack, the RadialStack, the AffineStack
-    _BINDINGS = ("_stack", "_pstack", "_rstack", "_astack")
+    # the CouplingStack, the PlanarStack, the RadialStack, the AffineStack, the
+    # MixedStack
+    _BINDINGS = ("_stack", "_pstack", "_rstack", "_astack", "_mstack")
 
     @classmethod
     def _drop_bindings(cls, attrs):
@@ -221,7 +280,7 @@ class Flow(nn.Module):
 
     def _row_stack(self, cls, layers):
         """The stack of class `cls` over `layers` (list(self.layers)), kept in
-        the slot the class names (_pstack, _rstack, _astack) and rebuilt when a layer or
+        the slot the class names (_pstack, _rstack, _astack, _mstack) and rebuilt when a layer or
         one of its parameters was replaced; a flow unpickled from before the
         slot existed builds it as well."""
         tensors = cls.layer_tensors

@@ -668,6 +668,102 @@ int cnf_affine_loss_vjp(int32_t dim, int32_t n_layers, const float* const* param
                         float grad_scale, float* loss_terms, float* grads, float* dx, int64_t B,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mixed row-wise flows: a Flow whose layers are PlanarLayers, RadialLayers and
+ * AffineConstantLayers (both parameters) of one width D, in any order, as ONE
+ * fused stack.  kinds: a HOST array of n_layers words, CNF_LAYER_PLANAR /
+ * CNF_LAYER_RADIAL / CNF_LAYER_AFFINE per layer.  Each layer is computed
+ * exactly as its own family documents it above (planar u_hat / tanh / log-det,
+ * radial h = 1 / (a + r), affine a rounded product followed by a rounded sum);
+ * the stack is never algebraically collapsed.  All fp32.
+ *   dim       D, 1..CNF_MAX_DIM;  n_layers  L, 1..CNF_MIXED_MAX_LAYERS
+ *             (< 1: CNF_ERR_DESC; above: CNF_ERR_UNSUPPORTED)
+ *   kinds     NULL: CNF_ERR_NULL; a value outside 0..2: CNF_ERR_DESC.  A stack
+ *             of a single kind is valid.
+ *   params    HOST array of DEVICE pointers in layer order, each layer's
+ *             tensors in its family's order: planar w, u, b; radial z0, a, b;
+ *             affine s, t -- 3 or 2 entries per layer (non-NULL, 4-byte aligned)
+ *   grads     flat in the same order (the state_dict order): 2 D + 1, D + 2 or
+ *             2 D floats per layer
+ *   logdet    [B], a row's: 0, then one rounded fp32 addition per planar layer
+ *             (that row's term) and per affine layer (its sum_d s, an fp32 sum
+ *             over d), in layer order, as Flow.forward accumulates it; a
+ *             radial layer adds nothing
+ *   gld       [B], a row's; an affine layer's grad s takes sum_rows gld
+ *   B         0..2^31 rows (CNF_ERR_BATCH otherwise)
+ *   workspace cnf_mixed_workspace_bytes(dim, n_layers, kinds, B) bytes of
+ *             DEVICE memory, no initialisation needed; one size serves every
+ *             entry point.  A call first writes one constant record of
+ *             2 DP + 8 floats per layer there with one small launch.
+ * In floats, with LPR, DP, r64, F and U as for the planar family and
+ * PW = L * (2 D + 2) + 4, the workspace holds
+ *   r64(L * (2 DP + 8)) + r64(PW) + r64(max(U * PW, 4 * F))
+ * There is no per-row tape and no layer is ever inverted (a contracting affine
+ * layer loses its input; a chain of radial inversions grows the error): the
+ * reverse mode keeps each layer's input in registers up to 10 layers, and
+ * above keeps every 16th and runs the row forward from it.
+ * Order of the checks, all before any HIP call: shape; kinds (NULL, then each
+ * value); for cnf_mixed_score the scoring arguments (as cnf_planar_score);
+ * batch; the parameter table entry by entry (NULL, then alignment); x /
+ * workspace NULL or short; x / workspace alignment; then per kind of call --
+ * forward: loss kind, loss NULLs, loss alignment, output alignment; reverse:
+ * grads NULL, the loss checks, alignment; predict and score: NULLs, alignment.
+ * B == 0 zeroes loss_terms / grads with memset nodes and launches no kernel.
+ * Deterministic as the planar family: per-block partial sums added in block
+ * order by a one-block follow-up launch, so two calls agree bitwise.  No float
+ * atomics, no allocation, no host synchronisation. */
+#define CNF_LAYER_PLANAR 0
+#define CNF_LAYER_RADIAL 1
+#define CNF_LAYER_AFFINE 2
+#define CNF_MIXED_MAX_LAYERS 64
+
+/* The sum over the layers of 2 D + 1 (planar), D + 2 (radial), 2 D (affine). */
+int cnf_mixed_param_count(int32_t dim, int32_t n_layers, const int32_t* kinds, int64_t* n_floats);
+int cnf_mixed_workspace_bytes(int32_t dim, int32_t n_layers, const int32_t* kinds, int64_t B,
+                              size_t* bytes);
+/* As cnf_planar_launch_plan; regt: every layer's input in registers (L <= 10,
+ * and D <= 10 or D > 16); rega: regt and LPR == 1; gacc: PW > 3072.  Without
+ * regt the reverse kernel is the checkpointed <LPR, CPL, 0, 0> instantiation. */
+int cnf_mixed_launch_plan(int32_t dim, int32_t n_layers, const int32_t* kinds, int64_t B,
+                          int32_t out[8]);
+
+/* The entry points below are their cnf_planar_* siblings with `kinds` after
+ * n_layers: the same arguments, outputs, NULL rules, loss kinds and `det`. */
+int cnf_mixed_forward(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                      const float* const* params, const float* x, float* z, float* logdet,
+                      float* z_all, int64_t B, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* loss_terms[3] = {sum loss, sum ce, sum ld} over the rows. */
+int cnf_mixed_forward_loss(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                           const float* const* params, const float* x, const int64_t* y,
+                           int32_t loss_kind, float det, float* z, float* logdet,
+                           float* loss_terms, int64_t B, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* As cnf_planar_predict word for word: centring, both softmaxes, the prior
+ * correction; logdet [B] of the centred rows, may be NULL. */
+int cnf_mixed_predict(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                      const float* const* params, const float* x, const float* log_priors,
+                      float* probs, float* logdet, int64_t B, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* As cnf_planar_score: ONE launch that ADDS into `record` the words that
+ * cnf_mixed_predict followed by cnf_metrics(probs, y, ...) would leave. */
+int cnf_mixed_score(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                    const float* const* params, const float* x, const float* log_priors,
+                    const int64_t* y, int32_t bins, int64_t* record, int64_t B, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* Reverse mode of cnf_mixed_forward: upstream gz [B][D], gz_all [L][B][D], gld
+ * [B] (each may be NULL = zero); writes grads [cnf_mixed_param_count]
+ * (overwritten) and dx [B][D] (may be NULL). */
+int cnf_mixed_vjp(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                  const float* const* params, const float* x, const float* gz,
+                  const float* gz_all, const float* gld, float* grads, float* dx, int64_t B,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* Fused forward + loss + reverse mode, as cnf_planar_loss_vjp. */
+int cnf_mixed_loss_vjp(int32_t dim, int32_t n_layers, const int32_t* kinds,
+                       const float* const* params, const float* x, const int64_t* y,
+                       int32_t loss_kind, float det, float grad_scale, float* loss_terms,
+                       float* grads, float* dx, int64_t B, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Which kernel family serves this descriptor's launches: "sgpr-fused"
  * (pipelined scalar weights, every output mode), "valu-fused" (strict_nan,
  * shapes whose Linears exceed 32 floats, misaligned views), "mfma-wide"

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <utility>
 #include <vector>
 
 #include "cnf.h"
@@ -224,6 +225,144 @@ static void row_family_check(const RowFamilyAbi& f, Rng& rng) {
   run(a, &t, ROW_SCORE, CNF_ERR_DESC);
 }
 
+// ---- the mixed family (cnf_mixed_*) ----------------------------------------------
+//
+// As above with `kinds` after n_layers: a heap block of exactly L words (one
+// when the shape is out of range and nothing may be read), seeded over the
+// three layer kinds, and a packed pointer table of exactly 3 or 2 entries per
+// layer.  Malformed kinds arrays (a value outside 0..2 at a seeded place, the
+// last included) and a null one are rejected directly after the shape.
+
+struct MixedArgs {
+  RowArgs r;
+  const int32_t* kinds;
+};
+
+static const std::vector<std::pair<int, int (*)(const MixedArgs&)>> kMixedEntries = {
+    {0, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_forward(a.dim, a.L, m.kinds, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb,
+                                nullptr);
+     }},
+    {ROW_LOSS, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_forward_loss(a.dim, a.L, m.kinds, a.params, a.x, g_i, a.kind, 1.f, g_f, g_f,
+                                     g_f, a.B, a.ws, a.wb, nullptr);
+     }},
+    {0, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_predict(a.dim, a.L, m.kinds, a.params, a.x, g_f, g_f, g_f, a.B, a.ws, a.wb,
+                                nullptr);
+     }},
+    {ROW_SCORE, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_score(a.dim, a.L, m.kinds, a.params, a.x, g_f, g_i, a.bins, g_i, a.B, a.ws,
+                              a.wb, nullptr);
+     }},
+    {ROW_BWD, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_vjp(a.dim, a.L, m.kinds, a.params, a.x, g_f, g_f, g_f, a.grads, g_f, a.B,
+                            a.ws, a.wb, nullptr);
+     }},
+    {ROW_BWD | ROW_LOSS, [](const MixedArgs& m) {
+       const RowArgs& a = m.r;
+       return cnf_mixed_loss_vjp(a.dim, a.L, m.kinds, a.params, a.x, g_i, a.kind, 1.f, 1.f, g_f,
+                                 a.grads, g_f, a.B, a.ws, a.wb, nullptr);
+     }}};
+
+template <class Rng>
+static void mixed_check(Rng& rng) {
+  auto U = [&](int lo, int hi) { return (int)std::uniform_int_distribution<int>(lo, hi)(rng); };
+  const int max_layers = CNF_MIXED_MAX_LAYERS;
+  const int32_t dim = U(0, 9) == 0 ? U(-3, 300) : U(1, CNF_MAX_DIM);
+  const int32_t L = U(0, 5) == 0 ? max_layers : U(0, 9) == 0 ? U(-2, max_layers + 6) : U(1, 12);
+  const int64_t B = U(0, 5) != 0 ? (int64_t)U(1, 1 << 20)
+                    : U(0, 1)    ? -(int64_t)U(1, 9)
+                                 : ((int64_t)1 << 31) + U(1, 9);
+  const bool shape_ok = dim >= 1 && dim <= CNF_MAX_DIM && L >= 1 && L <= max_layers;
+  const bool ok = shape_ok && B >= 0 && B <= ((int64_t)1 << 31);
+  const int nk = shape_ok ? L : 1;
+  std::vector<int32_t> kinds(nk);  // exactly L words
+  int n = 0;                       // entries of the packed table
+  int64_t want_nf = 0;
+  for (int l = 0; l < nk; ++l) {
+    kinds[l] = U(0, 2);
+    n += kinds[l] == CNF_LAYER_AFFINE ? 2 : 3;
+    want_nf += kinds[l] == CNF_LAYER_PLANAR ? 2 * dim + 1 : kinds[l] == CNF_LAYER_RADIAL ? dim + 2
+                                                                                         : 2 * dim;
+  }
+  std::vector<int32_t> bad = kinds;  // one value outside 0..2, the last place included
+  bad[U(0, 2) == 0 ? nk - 1 : U(0, nk - 1)] = U(0, 1) ? 3 + U(0, 9) : -1 - U(0, 9);
+  int64_t nf = -1;
+  size_t need = 0;
+  int32_t plan[8] = {0};
+  const int sp = cnf_mixed_param_count(dim, L, kinds.data(), &nf);
+  EXPECT(is_status(sp) && (sp == CNF_OK) == shape_ok);
+  if (shape_ok) EXPECT(nf == want_nf);
+  const int sw = cnf_mixed_workspace_bytes(dim, L, kinds.data(), B, &need);
+  EXPECT(is_status(sw) && (sw == CNF_OK) == ok);
+  const int sl = cnf_mixed_launch_plan(dim, L, kinds.data(), B, plan);
+  EXPECT(is_status(sl) && (sl == CNF_OK) == ok);
+  if (ok) EXPECT(need > 0 && need % 256 == 0 && plan[0] * plan[1] >= dim && plan[5] >= 1);
+  EXPECT(cnf_mixed_param_count(dim, L, kinds.data(), nullptr) == CNF_ERR_NULL);
+  EXPECT(cnf_mixed_workspace_bytes(dim, L, kinds.data(), B, nullptr) == CNF_ERR_NULL);
+  EXPECT(cnf_mixed_launch_plan(dim, L, kinds.data(), B, nullptr) == CNF_ERR_NULL);
+  if (shape_ok) {  // kinds directly after the shape, before the batch
+    EXPECT(cnf_mixed_param_count(dim, L, nullptr, &nf) == CNF_ERR_NULL);
+    EXPECT(cnf_mixed_param_count(dim, L, bad.data(), &nf) == CNF_ERR_DESC);
+    EXPECT(cnf_mixed_workspace_bytes(dim, L, nullptr, B, &need) == CNF_ERR_NULL);
+    EXPECT(cnf_mixed_workspace_bytes(dim, L, bad.data(), B, &need) == CNF_ERR_DESC);
+    EXPECT(cnf_mixed_launch_plan(dim, L, nullptr, B, plan) == CNF_ERR_NULL);
+    EXPECT(cnf_mixed_launch_plan(dim, L, bad.data(), B, plan) == CNF_ERR_DESC);
+  }
+
+  auto table = [&] {  // fresh, of exactly n fake aligned pointers
+    std::vector<const float*> t(n);
+    for (int i = 0; i < n; ++i) t[i] = reinterpret_cast<const float*>((uintptr_t)4096 + 64 * i);
+    return t;
+  };
+  const RowArgs good = {dim, L, nullptr, g_f, B, g_f, need, CNF_LOSS_CAL, 15, g_f};
+  // shape_only: the fault is answered before the batch is looked at
+  auto run = [&](RowArgs a, const int32_t* k, const std::vector<const float*>* t, int cats,
+                 int want, bool shape_only) {
+    a.params = t ? t->data() : nullptr;
+    for (const auto& e : kMixedEntries) {
+      if (cats && !(e.first & cats)) continue;
+      const int st = e.second(MixedArgs{a, k});
+      EXPECT(st < 0 && is_status(st));
+      const bool capped = (e.first & ROW_SCORE) && (dim < 2 || B > (1 << 26));
+      if (shape_only ? shape_ok : (ok && !capped)) EXPECT(st == want);
+    }
+  };
+  std::vector<const float*> t = table();
+  run(good, nullptr, &t, 0, CNF_ERR_NULL, true);               // a null kinds array
+  run(good, bad.data(), &t, 0, CNF_ERR_DESC, true);            // a malformed one
+  run(good, bad.data(), nullptr, 0, CNF_ERR_DESC, true);       // ... before the table is read
+  run(good, kinds.data(), nullptr, 0, CNF_ERR_NULL, false);    // a null table
+  const int at = U(0, 2) == 0 ? n - 1 : U(0, n - 1);           // ... entry, the last one included
+  t[at] = nullptr;
+  run(good, kinds.data(), &t, 0, CNF_ERR_NULL, false);
+  t = table();
+  t[at] = reinterpret_cast<const float*>((uintptr_t)4098);
+  run(good, kinds.data(), &t, 0, CNF_ERR_ALIGN, false);
+  t = table();
+  RowArgs a = good;
+  a.wb = need - 4;                                             // a short workspace
+  run(a, kinds.data(), &t, 0, CNF_ERR_NULL, false);
+  a = good;
+  a.x = reinterpret_cast<const float*>((const char*)g_f + 2);
+  run(a, kinds.data(), &t, 0, CNF_ERR_ALIGN, false);
+  a = good;
+  a.kind = U(2, 9);
+  run(a, kinds.data(), &t, ROW_LOSS, CNF_ERR_DESC, false);
+  a = good;
+  a.grads = nullptr;
+  run(a, kinds.data(), &t, ROW_BWD, CNF_ERR_NULL, false);
+  a = good;
+  a.bins = U(0, 1) ? -U(0, 3) : CNF_MAX_BINS + U(1, 9);
+  run(a, kinds.data(), &t, ROW_SCORE, CNF_ERR_DESC, false);
+}
+
 int main(int argc, char** argv) {
   const int iters = argc > 1 ? std::atoi(argv[1]) : 3000;
   std::mt19937_64 rng(20261018);
@@ -379,6 +518,7 @@ int main(int argc, char** argv) {
     }
     delete perms;
     for (const RowFamilyAbi* f : {&kPlanar, &kRadial, &kAffine}) row_family_check(*f, rng);
+    mixed_check(rng);
   }
   EXPECT(cnf_param_count(nullptr, nullptr) == CNF_ERR_NULL);
   EXPECT(n_ok > iters / 10);
