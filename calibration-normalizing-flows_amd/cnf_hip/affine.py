@@ -14,7 +14,9 @@ the flat gradient `loss_and_grads` writes, and `invalidate()` is a no-op, so
 the calibrator's epoch runner and its HIP-graph replay drive an AffineStack as
 they drive the other stacks.  The layers keep owning `s` and `t`.
 
-Everything that does not depend on the family is `cnf_hip.rowstack.RowStack`'s.
+Everything that does not depend on the family is `cnf_hip.rowstack.RowStack`'s,
+and so are `loss_and_grads`, `score` and `forward_autograd`; the launches here
+are the four the [1] log-det makes different.
 """
 import ctypes
 import operator
@@ -22,7 +24,7 @@ import operator
 import torch
 
 from . import _lib, rowstack
-from .stack import StackFn, _ptr, upstream_grads
+from .stack import _ptr, upstream_grads
 
 
 def workspace_bytes(dim, n_layers, B):
@@ -113,23 +115,6 @@ class AffineStack(rowstack.RowStack):
             grads.view(self.L, 2, self.dim)[:, 0, :] += gld
         return dx, grads
 
-    def loss_and_grads(self, x, y, kind=_lib.LOSS_CAL, det=1.0, grad_scale=1.0, need_dx=False,
-                       grads_out=None, terms_out=None):
-        """Fused forward + loss + reverse mode (cnf_affine_loss_vjp): returns
-        (terms[3], flat grads, dx) with terms the sums over this batch and
-        grads = grad_scale * d(sum of per-row loss)/d(params), s, t per layer."""
-        x = self._check_input(x.detach())
-        y = y.contiguous().to(torch.int64)
-        ws = self._ws(x)
-        dev = x.device
-        what = "loss_and_grads: output buffer"
-        grads = self._out_buffer(grads_out, self.param_count(), dev, what)
-        terms = self._out_buffer(terms_out, 3, dev, what)
-        dx = torch.empty_like(x) if need_dx else None
-        self._call("loss_vjp", x, ws, _ptr(y), ctypes.c_int32(kind), ctypes.c_float(det),
-                   ctypes.c_float(grad_scale), _ptr(terms), _ptr(grads), _ptr(dx))
-        return terms, grads, dx
-
     def predict(self, x, log_priors):
         """Calibrated probabilities softmax(log(softmax(flow(x - mean x)) + 1e-7)
         - log_priors) (Calibrator.predict, calibrators.py:40-44, 330-353): one
@@ -140,17 +125,3 @@ class AffineStack(rowstack.RowStack):
         probs = torch.empty_like(x)
         self._call("predict", x, ws, _ptr(lp), _ptr(probs))
         return probs
-
-    # -------------------------------------------------------------- autograd
-    def forward_autograd(self, x, want_all):
-        """Forward with gradients w.r.t. x and every parameter: backward is
-        cnf_affine_vjp.  Returns (z_all or z_final, logdet [1])."""
-        return _AffineFn.apply(self, want_all, x, *self._params)
-
-
-class _AffineFn(StackFn):
-    @staticmethod
-    def forward(ctx, stack, want_all, x, *params):
-        fin, ld, allt = stack.run(x, want_all=want_all)
-        StackFn.saved(ctx, stack, want_all, x)
-        return (allt if want_all else fin), ld

@@ -636,7 +636,8 @@ struct Affine {
   using Args = BwdArgs;
   static constexpr bool kLdScalar = true;  // the log-det is one number: [1]
   static const RowFamily& family() { return kFamily; }
-  static constexpr int grad_floats(int D) { return 2 * D; }  // s, t
+  static constexpr int grad_floats(int D, int = 0) { return 2 * D; }  // s, t
+  static int8_t* kinds(Ptrs&) { return nullptr; }
 
   static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool inv,
                    hipStream_t s) {

@@ -5,15 +5,14 @@
 // score variant (cnf_score.h), all fp32.
 //
 // Geometry, grid caps, workspace plan, shape dispatch, the lane helpers and
-// the call records are cnf_rowflow.h's, shared with cnf_planar.hip,
-// cnf_radial.hip and cnf_affine.hip; the kernel bodies are this file's own
-// text, as theirs are.  The host layer between the entry points
-// and the launches is this file's too: a mixed call carries `kinds`, its
-// parameter table has 3 or 2 entries per layer and its gradient is not a
-// multiple of one layer's size, which run_forward / run_predict / run_backward
-// have no word for.  It follows their order of checks line for line, with the
-// two checks of `kinds` directly after the shape check (include/cnf.h states
-// the order).
+// the host layer between the entry points and the launches (run_forward,
+// run_predict, run_backward over this file's `Mixed` policy) are
+// cnf_rowflow.h's, shared with cnf_planar.hip, cnf_radial.hip and
+// cnf_affine.hip; the kernel bodies are this file's own text, as theirs are
+// (DESIGN.md 7h).  What a mixed call has of its own -- `kinds`, checked
+// directly after the shape, a parameter table packed 3 or 2 entries per layer
+// and a gradient that is the per-kind sum -- the frame takes from
+// RowFamily::kind_tensors and Mixed::grad_floats(D, kind).
 //
 // Per-layer constants.  k_mixed_prep (L blocks) writes one record of
 // 2 DP + 8 floats per layer, whatever its kind (DP = LPR * CPL):
@@ -834,250 +833,96 @@ __global__ __launch_bounds__(kFinThreads) void k_mixed_finish(
   }
 }
 
-// ---- the host layer -----------------------------------------------------------
+// ---- launches -------------------------------------------------------------------
 
-// What every call checks first, in this order: shape, kinds (null, then each
-// value), batch, the packed parameter table (entry by entry: null, then
-// alignment), x / workspace null or short, x / workspace alignment.  Fills the
-// device-side table (three slots per layer) and the kinds, the geometry and
-// the plan.
-struct Stack {
-  Ptrs P;
-  Kinds K;
-  Geo g;
-  Plan p;
-  int64_t grad_total;
-};
+constexpr RowFamily kFamily{kMaxL, mixed_geometry, mixed_bwd_variant, 3, tensors_of};
 
-int check_kinds(int32_t dim, int32_t n_layers, const int32_t* kinds) {
-  const int st = check_shape(dim, n_layers, kMaxL);
-  if (st != CNF_OK) return st;
-  if (!kinds) return CNF_ERR_NULL;
-  for (int l = 0; l < n_layers; ++l)
-    if (kinds[l] < CNF_LAYER_PLANAR || kinds[l] > CNF_LAYER_AFFINE) return CNF_ERR_DESC;
-  return CNF_OK;
-}
+// What cnf_rowflow.h's launch layer asks of a family.
+struct Mixed {
+  // host only: the kernels take the two by value, separately
+  struct Table : Ptrs {
+    Kinds K;
+  };
+  using Args = BwdArgs;
+  static constexpr bool kLdScalar = false;  // the log-det is a row's: [B]
+  static const RowFamily& family() { return kFamily; }
+  static constexpr int grad_floats(int D, int kind) { return cnf::grad_floats(kind, D); }
+  static int8_t* kinds(Table& T) { return T.K.k; }
 
-int check_common(int32_t dim, int32_t n_layers, const int32_t* kinds, const float* const* params,
-                 const float* x, int64_t B, const void* ws, size_t ws_bytes, Stack* s) {
-  const int st = check_kinds(dim, n_layers, kinds);
-  if (st != CNF_OK) return st;
-  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
-  if (!params) return CNF_ERR_NULL;
-  int i = 0;
-  s->grad_total = 0;
-  for (int l = 0; l < kMaxL; ++l) {
-    s->K.k[l] = l < n_layers ? (int8_t)kinds[l] : 0;
-    for (int j = 0; j < 3; ++j) s->P.p[3 * l + j] = nullptr;
-    if (l >= n_layers) continue;
-    for (int j = 0; j < tensors_of(kinds[l]); ++j, ++i) {
-      if (!params[i]) return CNF_ERR_NULL;
-      if (mis4(params[i])) return CNF_ERR_ALIGN;
-      s->P.p[3 * l + j] = params[i];
+  static void prep(const Table& T, const Geo& g, int D, int L, float* blob, bool, hipStream_t s) {
+    hipLaunchKernelGGL(k_mixed_prep, dim3(L), dim3(64), 0, s, (const Ptrs&)T, T.K, blob, D, g.dp,
+                       g.cs);
+  }
+
+  template <int LPR, int CPL>
+  static void fwd(int blocks, const FwdCall& c, const Geo& g, const float* blob, float* part) {
+    hipLaunchKernelGGL((k_mixed_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x, blob,
+                       c.D, c.L, g.cs, c.B, c.z, c.ld, c.z_all, c.y, c.kind, c.det, part);
+  }
+
+  template <int LPR, int CPL>
+  static void predict(int blocks, const PredictCall& c, const Geo& g, const float* blob,
+                      const score::Args* sc) {
+    if (sc) {
+      hipLaunchKernelGGL((k_mixed_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, (float*)nullptr, (float*)nullptr,
+                         *sc);
+    } else {
+      hipLaunchKernelGGL((k_mixed_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, c.s,
+                         c.x, blob, c.lp, c.D, c.L, g.cs, c.B, c.probs, c.ld, score::Args{});
     }
-    s->grad_total += grad_floats(kinds[l], dim);
   }
-  s->g = mixed_geometry(dim, n_layers);
-  s->p = plan(s->g, n_layers, B);
-  if (B > 0 && (!x || !ws || ws_bytes < (size_t)s->p.total * sizeof(float))) return CNF_ERR_NULL;
-  if (mis4(x) || mis4(ws)) return CNF_ERR_ALIGN;
-  return CNF_OK;
-}
 
-void launch_prep(const Stack& s, int D, int L, float* blob, hipStream_t st) {
-  hipLaunchKernelGGL(k_mixed_prep, dim3(L), dim3(64), 0, st, s.P, s.K, blob, D, s.g.dp, s.g.cs);
-}
-
-void launch_finish(const Finish& f, const Stack& s, int D, int L, hipStream_t st) {
-  hipLaunchKernelGGL(k_mixed_finish, dim3(1), dim3(kFinThreads), 0, st, f.part, f.units, f.pw,
-                     f.nsum, f.sums, f.terms, f.grads, f.blob, s.P, s.K, D, L, s.g.dp, s.g.cs);
-}
-
-template <int LPR, int CPL>
-void launch_fwd(int blocks, const FwdCall& c, const Geo& g, const float* blob, float* part) {
-  hipLaunchKernelGGL((k_mixed_fwd<LPR, CPL>), dim3(blocks), dim3(kThreads), 0, c.s, c.x, blob, c.D,
-                     c.L, g.cs, c.B, c.z, c.ld, c.z_all, c.y, c.kind, c.det, part);
-}
-
-template <int LPR, int CPL>
-void launch_predict(int blocks, const PredictCall& c, const Geo& g, const float* blob,
-                    const score::Args* sc) {
-  if (sc) {
-    hipLaunchKernelGGL((k_mixed_predict<LPR, CPL, true>), dim3(blocks), dim3(kThreads), 0, c.s,
-                       c.x, blob, c.lp, c.D, c.L, g.cs, c.B, (float*)nullptr, (float*)nullptr,
-                       *sc);
-  } else {
-    hipLaunchKernelGGL((k_mixed_predict<LPR, CPL, false>), dim3(blocks), dim3(kThreads), 0, c.s,
-                       c.x, blob, c.lp, c.D, c.L, g.cs, c.B, c.probs, c.ld, score::Args{});
+  template <int LPR, int CPL>
+  static void bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
+    if (!mixed_bwd_variant(LPR, CPL, a.L).regt) {
+      hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a, a.blob);
+      return;
+    }
+    // regt and rega depend on the depth through L <= kRegL alone: the geometry's
+    // answer at kRegL
+    if constexpr (!mixed_bwd_variant(LPR, CPL, kRegL).regt) {
+      return;  // not reached: the branch above took every depth
+    } else if constexpr (mixed_bwd_variant(LPR, CPL, kRegL).rega) {
+      hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
+                         a, a.blob);
+    } else {
+      hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds,
+                         s, a, a.blob);
+    }
   }
-}
 
-template <int LPR, int CPL>
-void launch_bwd(int blocks, size_t lds, hipStream_t s, const BwdArgs& a) {
-  if (!mixed_bwd_variant(LPR, CPL, a.L).regt) {
-    hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, false, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-    return;
+  static void fill(BwdArgs& a, const BwdCall& c, float*) {  // no tape
+    a.gld = c.loss ? nullptr : c.gld;
+    a.det = c.det;
   }
-  // regt and rega depend on the depth through L <= kRegL alone: the geometry's
-  // answer at kRegL
-  if constexpr (!mixed_bwd_variant(LPR, CPL, kRegL).regt) {
-    return;  // not reached: the branch above took every depth
-  } else if constexpr (mixed_bwd_variant(LPR, CPL, kRegL).rega) {
-    hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, true, true>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-  } else {
-    hipLaunchKernelGGL((k_mixed_bwd<LPR, CPL, true, false>), dim3(blocks), dim3(kThreads), lds, s,
-                       a, a.blob);
-  }
-}
 
-// forward, forward + loss (c.loss): run_forward's order after the common checks
-int mixed_forward(const FwdCall& c, const int32_t* kinds) {
-  Stack s;
-  int st = check_common(c.D, c.L, kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, &s);
-  if (st != CNF_OK) return st;
-  if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
-  if (mis4(c.z) || mis4(c.ld) || mis4(c.z_all)) return CNF_ERR_ALIGN;
-  if (c.B == 0) return c.loss ? zero_floats(c.terms, 3, c.s) : CNF_OK;
-  const Geo& g = s.g;
-  float* w = static_cast<float*>(c.ws);
-  launch_prep(s, c.D, c.L, w + s.p.blob, c.s);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  const int blocks = fwd_blocks(g, c.B);
-  float* part = c.loss ? w + s.p.part : nullptr;
-  CNF_ROWFLOW_DISPATCH(launch_fwd, blocks, c, g, w + s.p.blob, part);
-  st = launch_status();
-  if (st != CNF_OK || !c.loss) return st;
-  launch_finish(Finish{part, blocks, 4, 0, w + s.p.sums, c.terms, nullptr, w + s.p.blob}, s, c.D,
-                c.L, c.s);
-  return launch_status();
-}
-
-// predict, or score (c.scoring): run_predict's order
-int mixed_predict(const PredictCall& c, const int32_t* kinds) {
-  Stack s;
-  int st = check_kinds(c.D, c.L, kinds);
-  if (st != CNF_OK) return st;
-  if (c.scoring && (st = score::check_args(c.D, c.bins, c.B, c.y, c.record)) != CNF_OK) return st;
-  st = check_common(c.D, c.L, kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, &s);
-  if (st != CNF_OK) return st;
-  if (c.B > 0 && (!c.lp || (!c.scoring && !c.probs))) return CNF_ERR_NULL;
-  if (mis4(c.lp) || mis4(c.probs) || mis4(c.ld)) return CNF_ERR_ALIGN;
-  if (c.B == 0) return CNF_OK;
-  const Geo& g = s.g;
-  float* w = static_cast<float*>(c.ws);
-  launch_prep(s, c.D, c.L, w + s.p.blob, c.s);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  score::Args sc;
-  if (c.scoring) sc = score::make_args(c.y, c.bins, c.record);
-  CNF_ROWFLOW_DISPATCH(launch_predict, fwd_blocks(g, c.B), c, g, w + s.p.blob,
-                       c.scoring ? &sc : nullptr);
-  return launch_status();
-}
-
-// reverse mode from upstream gradients, or fused with the loss (c.loss):
-// run_backward's order
-int mixed_backward(const BwdCall& c, const int32_t* kinds) {
-  Stack s;
-  int st = check_common(c.D, c.L, kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, &s);
-  if (st != CNF_OK) return st;
-  if (!c.grads) return CNF_ERR_NULL;
-  if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
-  if (mis4(c.gz) || mis4(c.gz_all) || mis4(c.gld) || mis4(c.grads) || mis4(c.dx))
-    return CNF_ERR_ALIGN;
-  if (c.B == 0) {
-    st = zero_floats(c.grads, (size_t)s.grad_total, c.s);
-    if (st == CNF_OK && c.loss) st = zero_floats(c.terms, 3, c.s);
-    return st;
+  static void finish(const Finish& f, const Table& T, int D, int L, const Geo& g, const BwdCall*,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_mixed_finish, dim3(1), dim3(kFinThreads), 0, s, f.part, f.units, f.pw,
+                       f.nsum, f.sums, f.terms, f.grads, f.blob, (const Ptrs&)T, T.K, D, L, g.dp,
+                       g.cs);
   }
-  const Geo& g = s.g;
-  float* w = static_cast<float*>(c.ws);
-  launch_prep(s, c.D, c.L, w + s.p.blob, c.s);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  const int blocks = bwd_blocks(g, c.B);
-  const int units = bwd_units(g, c.B);
-  size_t lds = 0;
-  if (g.gacc) {
-    st = zero_floats(w + s.p.part, (size_t)units * g.pw, c.s);
-    if (st != CNF_OK) return st;
-  } else {
-    lds = (size_t)kWaves * g.pw * sizeof(float);
-  }
-  BwdArgs a;
-  a.x = c.x;
-  a.blob = w + s.p.blob;
-  a.y = c.loss ? c.y : nullptr;
-  a.gz = c.loss ? nullptr : c.gz;
-  a.gz_all = c.loss ? nullptr : c.gz_all;
-  a.gld = c.loss ? nullptr : c.gld;
-  a.dx = c.dx;
-  a.part = w + s.p.part;
-  a.B = c.B;
-  a.D = c.D;
-  a.L = c.L;
-  a.cs = g.cs;
-  a.ps = g.ps;
-  a.pw = g.pw;
-  a.gacc = g.gacc ? 1 : 0;
-  a.kind = c.kind;
-  a.det = c.det;
-  a.gscale = c.gscale;
-  CNF_ROWFLOW_DISPATCH(launch_bwd, blocks, lds, c.s, a);
-  st = launch_status();
-  if (st != CNF_OK) return st;
-  launch_finish(Finish{a.part, units, g.pw, c.L * g.ps, w + s.p.sums, c.loss ? c.terms : nullptr,
-                       c.grads, w + s.p.blob},
-                s, c.D, c.L, c.s);
-  return launch_status();
-}
+};
 
 }  // namespace
 }  // namespace cnf
 
 extern "C" int cnf_mixed_param_count(int32_t dim, int32_t n_layers, const int32_t* kinds,
                                      int64_t* n_floats) {
-  if (!n_floats) return CNF_ERR_NULL;
-  const int st = cnf::check_kinds(dim, n_layers, kinds);
-  if (st != CNF_OK) return st;
-  int64_t n = 0;
-  for (int l = 0; l < n_layers; ++l) n += cnf::grad_floats(kinds[l], dim);
-  *n_floats = n;
-  return CNF_OK;
+  return cnf::rowflow::param_count(cnf::kFamily, cnf::Mixed::grad_floats, dim, n_layers, n_floats,
+                                   kinds);
 }
 
 extern "C" int cnf_mixed_workspace_bytes(int32_t dim, int32_t n_layers, const int32_t* kinds,
                                          int64_t B, size_t* bytes) {
-  using namespace cnf::rowflow;
-  if (!bytes) return CNF_ERR_NULL;
-  const int st = cnf::check_kinds(dim, n_layers, kinds);
-  if (st != CNF_OK) return st;
-  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
-  *bytes = (size_t)plan(cnf::mixed_geometry(dim, n_layers), n_layers, B).total * sizeof(float);
-  return CNF_OK;
+  return cnf::rowflow::workspace_bytes(cnf::kFamily, dim, n_layers, B, bytes, kinds);
 }
 
 extern "C" int cnf_mixed_launch_plan(int32_t dim, int32_t n_layers, const int32_t* kinds,
                                      int64_t B, int32_t out[8]) {
-  using namespace cnf::rowflow;
-  if (!out) return CNF_ERR_NULL;
-  const int st = cnf::check_kinds(dim, n_layers, kinds);
-  if (st != CNF_OK) return st;
-  if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
-  const Geo g = cnf::mixed_geometry(dim, n_layers);
-  const BwdVariant v = cnf::mixed_bwd_variant(g.lpr, g.cpl, n_layers);
-  out[0] = g.lpr;
-  out[1] = g.cpl;
-  out[2] = v.regt ? 1 : 0;
-  out[3] = v.rega ? 1 : 0;
-  out[4] = g.gacc ? 1 : 0;
-  out[5] = fwd_blocks(g, B);
-  out[6] = bwd_blocks(g, B);
-  out[7] = bwd_units(g, B);
-  return CNF_OK;
+  return cnf::rowflow::launch_plan(cnf::kFamily, dim, n_layers, B, out, kinds);
 }
 
 extern "C" int cnf_mixed_forward(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1085,9 +930,10 @@ extern "C" int cnf_mixed_forward(int32_t dim, int32_t n_layers, const int32_t* k
                                  float* logdet, float* z_all, int64_t B, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_forward");
-  return cnf::mixed_forward({dim, n_layers, params, x, nullptr, 0, 0.f, z, logdet, z_all, nullptr,
-                             B, workspace, workspace_bytes, (hipStream_t)stream, false, false},
-                            kinds);
+  return cnf::rowflow::run_forward<cnf::Mixed>({dim, n_layers, params, x, nullptr, 0, 0.f, z,
+                                                logdet, z_all, nullptr, B, workspace,
+                                                workspace_bytes, (hipStream_t)stream, false, false,
+                                                kinds});
 }
 
 extern "C" int cnf_mixed_forward_loss(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1096,10 +942,10 @@ extern "C" int cnf_mixed_forward_loss(int32_t dim, int32_t n_layers, const int32
                                       float* logdet, float* loss_terms, int64_t B, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_forward_loss");
-  return cnf::mixed_forward({dim, n_layers, params, x, y, loss_kind, det, z, logdet, nullptr,
-                             loss_terms, B, workspace, workspace_bytes, (hipStream_t)stream, true,
-                             false},
-                            kinds);
+  return cnf::rowflow::run_forward<cnf::Mixed>({dim, n_layers, params, x, y, loss_kind, det, z,
+                                                logdet, nullptr, loss_terms, B, workspace,
+                                                workspace_bytes, (hipStream_t)stream, true, false,
+                                                kinds});
 }
 
 extern "C" int cnf_mixed_predict(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1107,9 +953,10 @@ extern "C" int cnf_mixed_predict(int32_t dim, int32_t n_layers, const int32_t* k
                                  const float* log_priors, float* probs, float* logdet, int64_t B,
                                  void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_predict");
-  return cnf::mixed_predict({dim, n_layers, params, x, log_priors, probs, logdet, nullptr, 0,
-                             nullptr, B, workspace, workspace_bytes, (hipStream_t)stream, false},
-                            kinds);
+  return cnf::rowflow::run_predict<cnf::Mixed>({dim, n_layers, params, x, log_priors, probs,
+                                                logdet, nullptr, 0, nullptr, B, workspace,
+                                                workspace_bytes, (hipStream_t)stream, false,
+                                                kinds});
 }
 
 extern "C" int cnf_mixed_score(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1117,9 +964,9 @@ extern "C" int cnf_mixed_score(int32_t dim, int32_t n_layers, const int32_t* kin
                                const int64_t* y, int32_t bins, int64_t* record, int64_t B,
                                void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_score");
-  return cnf::mixed_predict({dim, n_layers, params, x, log_priors, nullptr, nullptr, y, bins,
-                             record, B, workspace, workspace_bytes, (hipStream_t)stream, true},
-                            kinds);
+  return cnf::rowflow::run_predict<cnf::Mixed>({dim, n_layers, params, x, log_priors, nullptr,
+                                                nullptr, y, bins, record, B, workspace,
+                                                workspace_bytes, (hipStream_t)stream, true, kinds});
 }
 
 extern "C" int cnf_mixed_vjp(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1127,10 +974,10 @@ extern "C" int cnf_mixed_vjp(int32_t dim, int32_t n_layers, const int32_t* kinds
                              const float* gz_all, const float* gld, float* grads, float* dx,
                              int64_t B, void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_vjp");
-  return cnf::mixed_backward({dim, n_layers, params, x, nullptr, 0, 0.f, 1.f, gz, gz_all, gld,
-                              nullptr, grads, dx, B, workspace, workspace_bytes,
-                              (hipStream_t)stream, false},
-                             kinds);
+  return cnf::rowflow::run_backward<cnf::Mixed>({dim, n_layers, params, x, nullptr, 0, 0.f, 1.f,
+                                                 gz, gz_all, gld, nullptr, grads, dx, B, workspace,
+                                                 workspace_bytes, (hipStream_t)stream, false,
+                                                 kinds});
 }
 
 extern "C" int cnf_mixed_loss_vjp(int32_t dim, int32_t n_layers, const int32_t* kinds,
@@ -1139,8 +986,8 @@ extern "C" int cnf_mixed_loss_vjp(int32_t dim, int32_t n_layers, const int32_t* 
                                   float* loss_terms, float* grads, float* dx, int64_t B,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   CNF_RANGE("cnf_mixed_loss_vjp");
-  return cnf::mixed_backward({dim, n_layers, params, x, y, loss_kind, det, grad_scale, nullptr,
-                              nullptr, nullptr, loss_terms, grads, dx, B, workspace,
-                              workspace_bytes, (hipStream_t)stream, true},
-                             kinds);
+  return cnf::rowflow::run_backward<cnf::Mixed>({dim, n_layers, params, x, y, loss_kind, det,
+                                                 grad_scale, nullptr, nullptr, nullptr, loss_terms,
+                                                 grads, dx, B, workspace, workspace_bytes,
+                                                 (hipStream_t)stream, true, kinds});
 }

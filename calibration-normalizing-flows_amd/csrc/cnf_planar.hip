@@ -596,7 +596,8 @@ struct Planar {
   using Args = BwdArgs;
   static constexpr bool kLdScalar = false;  // the log-det is a row's: [B]
   static const RowFamily& family() { return kFamily; }
-  static constexpr int grad_floats(int D) { return 2 * D + 1; }  // w, u, b
+  static constexpr int grad_floats(int D, int = 0) { return 2 * D + 1; }  // w, u, b
+  static int8_t* kinds(Ptrs&) { return nullptr; }
 
   static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool, hipStream_t s) {
     hipLaunchKernelGGL(k_planar_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);

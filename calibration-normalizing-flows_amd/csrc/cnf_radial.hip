@@ -637,7 +637,8 @@ struct Radial {
   using Args = BwdArgs;
   static constexpr bool kLdScalar = false;  // no log-det at all
   static const RowFamily& family() { return kFamily; }
-  static constexpr int grad_floats(int D) { return D + 2; }  // z0, a, b
+  static constexpr int grad_floats(int D, int = 0) { return D + 2; }  // z0, a, b
+  static int8_t* kinds(Ptrs&) { return nullptr; }
 
   static void prep(const Ptrs& P, const Geo& g, int D, int L, float* blob, bool, hipStream_t s) {
     hipLaunchKernelGGL(k_radial_prep, dim3(L), dim3(64), 0, s, P, blob, D, g.dp, g.cs);

@@ -1,6 +1,6 @@
 // What the row-wise flow families (cnf_planar.hip, cnf_radial.hip,
-// cnf_affine.hip) share: the grid constants, the geometry of a row in lanes, the
-// workspace plan, the shape dispatch, the lane helpers, and the whole host layer
+// cnf_affine.hip, cnf_mixed.hip) share: the grid constants, the geometry of a
+// row in lanes, the workspace plan, the shape dispatch, the lane helpers, and the whole host layer
 // between the extern "C" entry points and the launches: the argument checks
 // and their order, the B == 0 contract, the prep launch, the choice between
 // workspace and LDS records, the finish launch and the status tail
@@ -11,7 +11,10 @@
 // workspace (1, or 0 for a family without such a tape) -- which it passes to
 // geometry(), in its parameter tensors per layer (RowFamily::tensors), and in
 // what its policy type says (below, "the launch layer"): its kernels'
-// argument lists and the gradient floats of a layer.
+// argument lists and the gradient floats of a layer.  The mixed family's layers
+// differ in kind: its calls carry `kinds`, checked directly after the shape,
+// and a layer's tensors and gradient floats go by its kind
+// (RowFamily::kind_tensors, grad_floats(D, kind)).
 //
 // Everything here is either host code or an inline device function that was
 // one already; the kernel bodies stay in their files, because wrapping kernel
@@ -196,12 +199,6 @@ __device__ __forceinline__ void row_softmax(const float* xv, int gl, int D, int6
     }                                                    \
   } while (0)
 
-inline int check_shape(int32_t dim, int32_t n_layers, int max_layers) {
-  if (dim < 1 || n_layers < 1) return CNF_ERR_DESC;
-  if (dim > CNF_MAX_DIM || n_layers > max_layers) return CNF_ERR_UNSUPPORTED;
-  return CNF_OK;
-}
-
 // Which instantiation of a family's reverse-mode kernel a launch takes: regt,
 // the tape in registers (L <= kRegL); rega, per-lane accumulators on top of it
 // (the family says for which geometries).  One helper per family answers it,
@@ -212,30 +209,57 @@ struct BwdVariant {
 
 // A family: its layer cap, its geometry(D, L, cs, ps, tf) with the family words
 // filled in, its reverse-mode variant for a geometry and depth, and its
-// parameter tensors per layer.
+// parameter tensors per layer.  A family whose layers differ in kind (mixed)
+// also says how many of those tensors a layer of a kind has; its calls then
+// carry `kinds`, and the caller's table is packed by those counts.
 struct RowFamily {
   int max_layers;
   Geo (*geo)(int D, int L);
   BwdVariant (*bwd)(int lpr, int cpl, int L);
   int tensors = 3;
+  int (*kind_tensors)(int kind) = nullptr;
 };
 
-// Common argument checks; fills the pointer table (tensors * max_layers
-// entries, null past the tensors * n_layers given), the geometry and the plan.
-inline int check_common(const RowFamily& f, int32_t dim, int32_t n_layers,
-                        const float* const* params, const float* x, int64_t B, const void* ws,
-                        size_t ws_bytes, const float** table, Geo* g, Plan* p) {
-  const int st = check_shape(dim, n_layers, f.max_layers);
+// What every entry point checks first: the shape, then, for a family that
+// takes them, `kinds` null and each of its values in order.
+static inline int check_head(const RowFamily& f, int32_t dim, int32_t n_layers,
+                             const int32_t* kinds) {
+  if (dim < 1 || n_layers < 1) return CNF_ERR_DESC;
+  if (dim > CNF_MAX_DIM || n_layers > f.max_layers) return CNF_ERR_UNSUPPORTED;
+  if (!f.kind_tensors) return CNF_OK;
+  if (!kinds) return CNF_ERR_NULL;
+  for (int l = 0; l < n_layers; ++l)
+    if (kinds[l] < CNF_LAYER_PLANAR || kinds[l] > CNF_LAYER_AFFINE) return CNF_ERR_DESC;
+  return CNF_OK;
+}
+
+// Common argument checks; fills the pointer table (tensors slots per layer,
+// max_layers layers; null where the layer has no such tensor or is not given),
+// the table's kinds (`kd`, null for a family of one kind; 0 past n_layers), the
+// geometry and the plan.  The caller's table is read entry by entry and no
+// further than the layers' tensors add up to.
+static inline int check_common(const RowFamily& f, int32_t dim, int32_t n_layers,
+                               const int32_t* kinds, const float* const* params, const float* x,
+                               int64_t B, const void* ws, size_t ws_bytes, const float** table,
+                               int8_t* kd, Geo* g, Plan* p) {
+  const int st = check_head(f, dim, n_layers, kinds);
   if (st != CNF_OK) return st;
   if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
   if (!params) return CNF_ERR_NULL;
   const int nt = f.tensors;
-  for (int i = 0; i < nt * n_layers; ++i) {
-    if (!params[i]) return CNF_ERR_NULL;
-    if (mis4(params[i])) return CNF_ERR_ALIGN;
-    table[i] = params[i];
+  for (int l = 0, i = 0; l < f.max_layers; ++l) {
+    const int n = l >= n_layers ? 0 : f.kind_tensors ? f.kind_tensors(kinds[l]) : nt;
+    if (kd) kd[l] = l < n_layers ? (int8_t)kinds[l] : 0;
+    for (int j = 0; j < nt; ++j) {
+      const float* q = nullptr;
+      if (j < n) {
+        q = params[i++];
+        if (!q) return CNF_ERR_NULL;
+        if (mis4(q)) return CNF_ERR_ALIGN;
+      }
+      table[nt * l + j] = q;
+    }
   }
-  for (int i = nt * n_layers; i < nt * f.max_layers; ++i) table[i] = nullptr;
   *g = f.geo(dim, n_layers);
   *p = plan(*g, n_layers, B);
   if (B > 0 && (!x || !ws || ws_bytes < (size_t)p->total * sizeof(float))) return CNF_ERR_NULL;
@@ -245,9 +269,9 @@ inline int check_common(const RowFamily& f, int32_t dim, int32_t n_layers,
 
 // the body of cnf_<family>_workspace_bytes
 inline int workspace_bytes(const RowFamily& f, int32_t dim, int32_t n_layers, int64_t B,
-                           size_t* bytes) {
+                           size_t* bytes, const int32_t* kinds = nullptr) {
   if (!bytes) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers, f.max_layers);
+  const int st = check_head(f, dim, n_layers, kinds);
   if (st != CNF_OK) return st;
   if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
   *bytes = (size_t)plan(f.geo(dim, n_layers), n_layers, B).total * sizeof(float);
@@ -257,9 +281,9 @@ inline int workspace_bytes(const RowFamily& f, int32_t dim, int32_t n_layers, in
 // the body of cnf_<family>_launch_plan: what a call of this shape would launch,
 // from the functions the launches themselves use.  Host only.
 inline int launch_plan(const RowFamily& f, int32_t dim, int32_t n_layers, int64_t B,
-                       int32_t* out) {
+                       int32_t* out, const int32_t* kinds = nullptr) {
   if (!out) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers, f.max_layers);
+  const int st = check_head(f, dim, n_layers, kinds);
   if (st != CNF_OK) return st;
   if (B < 0 || B > kMaxRows) return CNF_ERR_BATCH;
   const Geo g = f.geo(dim, n_layers);
@@ -275,13 +299,23 @@ inline int launch_plan(const RowFamily& f, int32_t dim, int32_t n_layers, int64_
   return CNF_OK;
 }
 
+// gradient (= parameter) floats of a stack: the sum over its layers, each of
+// its kind (kind 0 where the family has one kind and `kinds` is null)
+static inline int64_t grad_total(int (*grad_floats)(int D, int kind), int D, int L,
+                                 const int32_t* kinds) {
+  int64_t n = 0;
+  for (int l = 0; l < L; ++l) n += grad_floats(D, kinds ? kinds[l] : 0);
+  return n;
+}
+
 // the body of cnf_<family>_param_count
-static inline int param_count(const RowFamily& f, int (*grad_floats)(int D), int32_t dim,
-                              int32_t n_layers, int64_t* n_floats) {
+static inline int param_count(const RowFamily& f, int (*grad_floats)(int D, int kind), int32_t dim,
+                              int32_t n_layers, int64_t* n_floats,
+                              const int32_t* kinds = nullptr) {
   if (!n_floats) return CNF_ERR_NULL;
-  const int st = check_shape(dim, n_layers, f.max_layers);
+  const int st = check_head(f, dim, n_layers, kinds);
   if (st != CNF_OK) return st;
-  *n_floats = (int64_t)n_layers * grad_floats(dim);
+  *n_floats = grad_total(grad_floats, dim, n_layers, kinds);
   return CNF_OK;
 }
 
@@ -289,12 +323,15 @@ static inline int param_count(const RowFamily& f, int (*grad_floats)(int D), int
 //
 // One record per kind of call, with every argument any family has; an entry
 // point whose family lacks one passes null / 0 (mis4(nullptr) is false, so one
-// alignment line serves all).  run_forward, run_predict and run_backward own
-// the order of the checks, which is part of the ABI (DESIGN.md 7k states it).
+// alignment line serves all; `kinds`, the last word of each record, is null
+// unless the family's layers differ in kind).  run_forward, run_predict and
+// run_backward own the order of the checks, which is part of the ABI
+// (DESIGN.md 7k states it).
 // A family's policy type F, defined in its file's anonymous namespace, supplies
-//   Table, Args             its Ptrs and BwdArgs
+//   Table, Args             its Ptrs (mixed: its Ptrs and Kinds) and BwdArgs
 //   family()                its RowFamily
-//   grad_floats(D)          gradient (= parameter) floats per layer
+//   grad_floats(D, kind)    gradient (= parameter) floats of a layer
+//   kinds(P)                the table's kinds, int8_t[max_layers]; null for one kind
 //   kLdScalar               whether the log-det is one number [1], not a row's [B]
 //   prep(P, g, D, L, blob, inv, s)                 the constant-record launch
 //   fwd / predict / bwd <LPR, CPL>(...)            its kernels' launches
@@ -314,6 +351,7 @@ struct FwdCall {
   size_t ws_bytes;
   hipStream_t s;
   bool loss, inv;
+  const int32_t* kinds = nullptr;
 };
 
 struct PredictCall {
@@ -329,6 +367,7 @@ struct PredictCall {
   size_t ws_bytes;
   hipStream_t s;
   bool scoring;
+  const int32_t* kinds = nullptr;
 };
 
 struct BwdCall {
@@ -345,6 +384,7 @@ struct BwdCall {
   size_t ws_bytes;
   hipStream_t s;
   bool loss;
+  const int32_t* kinds = nullptr;
 };
 
 // What a finish launch adds up: `units` records of `pw` words at `part`, the
@@ -373,7 +413,8 @@ int run_forward(const FwdCall& c) {
   typename F::Table P;
   Geo g;
   Plan p;
-  int st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  int st = check_common(F::family(), c.D, c.L, c.kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p,
+                        F::kinds(P), &g, &p);
   if (st != CNF_OK) return st;
   if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
   if (mis4(c.z) || mis4(c.ld) || mis4(c.z_all)) return CNF_ERR_ALIGN;
@@ -402,10 +443,11 @@ int run_predict(const PredictCall& c) {
   typename F::Table P;
   Geo g;
   Plan p;
-  int st = check_shape(c.D, c.L, F::family().max_layers);
+  int st = check_head(F::family(), c.D, c.L, c.kinds);
   if (st != CNF_OK) return st;
   if (c.scoring && (st = score::check_args(c.D, c.bins, c.B, c.y, c.record)) != CNF_OK) return st;
-  st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  st = check_common(F::family(), c.D, c.L, c.kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p,
+                    F::kinds(P), &g, &p);
   if (st != CNF_OK) return st;
   if (c.B > 0 && (!c.lp || (!c.scoring && !c.probs))) return CNF_ERR_NULL;
   if (mis4(c.lp) || mis4(c.probs) || mis4(c.ld)) return CNF_ERR_ALIGN;
@@ -427,14 +469,15 @@ int run_backward(const BwdCall& c) {
   typename F::Table P;
   Geo g;
   Plan p;
-  int st = check_common(F::family(), c.D, c.L, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p, &g, &p);
+  int st = check_common(F::family(), c.D, c.L, c.kinds, c.params, c.x, c.B, c.ws, c.ws_bytes, P.p,
+                        F::kinds(P), &g, &p);
   if (st != CNF_OK) return st;
   if (!c.grads) return CNF_ERR_NULL;
   if (c.loss && (st = check_loss(c.kind, c.y, c.terms, c.B)) != CNF_OK) return st;
   if (mis4(c.gz) || mis4(c.gz_all) || mis4(c.gld) || mis4(c.grads) || mis4(c.dx))
     return CNF_ERR_ALIGN;
   if (c.B == 0) {
-    st = zero_floats(c.grads, (size_t)c.L * F::grad_floats(c.D), c.s);
+    st = zero_floats(c.grads, (size_t)grad_total(F::grad_floats, c.D, c.L, c.kinds), c.s);
     if (st == CNF_OK && c.loss) st = zero_floats(c.terms, 3, c.s);
     return st;
   }

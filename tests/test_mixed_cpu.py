@@ -5,8 +5,8 @@ reference's record, the dispatch rule of flows.flows, the log-det shape rule
 against the CPU layer loop, MixedFlow and pickling.
 
 Every launching call below carries at least one fault, so it returns before
-any HIP call; the pointers are fake (the table machinery is
-tests/test_rowflow_args_cpu.py's, with `kinds` after n_layers)."""
+any HIP call; the pointers are fake (the fault table is
+tests/test_rowflow_args_cpu.py's, of which mixed is the fourth family)."""
 import ctypes
 import itertools
 import os
@@ -115,91 +115,23 @@ def test_query_argument_errors():
 
 # ---- C ABI: every argument error of every entry point, and their order -----------------------
 
-KINDS = [0, 2]                  # planar + affine: a packed table of 3 + 2 entries
-N_TABLE = 5
-FAULTS = dict(T.FAULTS)
-FAULTS.update({
-    "kinds_null": ({"kinds": None}, -1),
-    "kinds_bad_first": ({"kinds": [3, 2]}, -2),
-    "kinds_bad_last": ({"kinds": [0, -1]}, -2),
-})
-PAIRS = list(T.PAIRS) + [
-    ("dim_big", "kinds_null"),            # the shape before kinds: -3
-    ("layers_big", "kinds_bad_first"),
-    ("kinds_null", "batch_neg"),          # kinds directly after the shape: -1 ...
-    ("kinds_bad_last", "batch_neg"),      # ... -2
-    ("kinds_bad_first", "table_null"),    # -2
-    ("kinds_null", "entry_mis_first"),    # -1
-    ("kinds_null", "bins_zero"),          # score: kinds before the scoring arguments: -1
-    ("kinds_bad_last", "record_null"),    # -2
-    ("kinds_bad_first", "x_mis"),
-]
-
-
-def _names(entry):
-    return ("dim L kinds params x " + T.SIGS["planar"][entry] + " " + T.TAIL).split()
-
-
-def _applies(fault, names):
-    over = FAULTS[fault][0]
-    return all(over["only"] in names if k == "only" else k in names or k == "bad" for k in over)
-
-
-def _cases():
-    out = []
-    for entry in ENTRY_NAMES:
-        names = _names(entry)
-        for f in FAULTS:
-            if _applies(f, names):
-                out.append((entry, (f,), FAULTS[f][1]))
-        for a, b in PAIRS:
-            if _applies(a, names) and _applies(b, names):
-                assert FAULTS[a][1] != FAULTS[b][1], (a, b)
-                out.append((entry, (a, b), FAULTS[a][1]))
-    return out
-
-
-CASES = _cases()
+# The table is tests/test_rowflow_args_cpu.py's, where mixed is the fourth family
+# (its head carries `kinds`, its packed table has 3 + 2 entries); its mixed rows
+# run here under the ids they have always had.
+KINDS = T.KINDS
+CASES = [(entry, fs, st) for fam, entry, fs, st in T.CASES if fam == "mixed"]
 IDS = ["%s-%s" % (entry, "+".join(fs)) for entry, fs, _ in CASES]
-
-
-def call(entry, faults):
-    names = _names(entry)
-    vals = dict(T.GOOD)
-    vals["wb"] = mixed.workspace_bytes(T.D, KINDS, T.B)
-    table = [4096 + 64 * i for i in range(N_TABLE)]
-    kinds, null_table = list(KINDS), False
-    for f in faults:
-        for k, v in FAULTS[f][0].items():
-            if k == "bad":
-                for i, p in v:
-                    table[i] = p
-            elif k == "params":
-                null_table = True
-            elif k == "kinds":
-                kinds = v
-            elif k == "wb":
-                vals["wb"] += v
-            elif k != "only":
-                vals[k] = v
-    vals["params"] = None if null_table else (P * N_TABLE)(*table)
-    vals["kinds"] = None if kinds is None else _kinds(kinds)
-    args = []
-    for n in names:
-        v = vals.get(n, 16)                      # any other argument: a fake aligned pointer
-        args.append(v if n in ("params", "kinds") else T.CTYPES.get(n, P)(v))
-    return getattr(_lib.lib(), "cnf_mixed_" + entry)(*args)
 
 
 @pytest.mark.parametrize("entry,faults,status", CASES, ids=IDS)
 def test_status_and_precedence(entry, faults, status):
-    assert T.L == len(KINDS) and call(entry, faults) == status
+    assert T.L == len(KINDS) and T.call("mixed", entry, faults) == status
 
 
 def test_table_covers_every_entry_point_and_fault():
     assert len(IDS) == len(set(IDS))
-    assert {f for _, fs, _ in CASES for f in fs} == set(FAULTS)
-    assert {fs for _, fs, _ in CASES if len(fs) == 2} == set(PAIRS)
+    assert {f for _, fs, _ in CASES for f in fs} == set(T.FAULTS)
+    assert {fs for _, fs, _ in CASES if len(fs) == 2} == set(T.PAIRS)
     for entry in ENTRY_NAMES:
         mine = {fs for e, fs, _ in CASES if e == entry}
         assert {("kinds_null",), ("kinds_bad_first",), ("kinds_bad_last",), ("dim_big", "kinds_null"),
@@ -228,9 +160,9 @@ def test_packed_table_is_read_to_its_last_entry():
 
 @pytest.mark.parametrize("entry", ["forward", "predict", "score"])
 def test_empty_batch_without_outputs_needs_no_device(entry):
-    names = _names(entry)
+    names, nt = T.names("mixed", entry), T.N_TABLE["mixed"]
     vals = dict(T.GOOD, B=0, wb=0, record=16, kinds=_kinds(KINDS),
-                params=(P * N_TABLE)(*[4096 + 64 * i for i in range(N_TABLE)]))
+                params=(P * nt)(*[4096 + 64 * i for i in range(nt)]))
     args = [vals[n] if n in ("params", "kinds") else T.CTYPES.get(n, P)(vals.get(n, 0))
             for n in names]
     assert getattr(_lib.lib(), "cnf_mixed_" + entry)(*args) == 0

@@ -1,18 +1,21 @@
 """The argument checks of every launching cnf_planar_* / cnf_radial_* /
-cnf_affine_* entry point, and their order, without a GPU.
+cnf_affine_* / cnf_mixed_* entry point, and their order, without a GPU.
 
 Every call below carries at least one fault, so it returns before any HIP
-call; the pointers are fake.  One table serves the three families: an entry
-point is its argument names (SIGS), a fault is a set of overrides of the good
-call plus the status it earns alone (FAULTS), and a fault applies to an entry
-point that has the arguments it overrides.  PAIRS pins the order of the
-checks: a call carrying both faults of a pair returns the status of the first.
+call; the pointers are fake.  One table serves the four families: an entry
+point is its argument names (HEADS, SIGS), a fault is a set of overrides of the
+good call plus the status it earns alone (FAULTS), and a fault applies to an
+entry point that has the arguments it overrides -- the `kinds` faults to the
+mixed family's, whose head carries `kinds` after n_layers and whose parameter
+table is packed, 3 + 2 entries for KINDS.  PAIRS pins the order of the checks:
+a call carrying both faults of a pair returns the status of the first.
 
-The order: shape, batch, parameter table (entry by entry: null,
-then alignment), x / workspace null or short, x / workspace alignment; then
-per kind of call -- forward: loss kind, loss nulls, loss alignment, output
-alignment; reverse: grads null, the loss checks, alignment; predict: nulls,
-alignment; score: shape, the scoring arguments, then as predict."""
+The order: shape, kinds (null, then each value), batch,
+parameter table (entry by entry: null, then alignment), x / workspace null or
+short, x / workspace alignment; then per kind of call -- forward: loss kind,
+loss nulls, loss alignment, output alignment; reverse: grads null, the loss
+checks, alignment; predict: nulls, alignment; score: shape, kinds, the scoring
+arguments, then as predict."""
 import ctypes
 
 import pytest
@@ -22,9 +25,12 @@ from cnf_hip import _lib, rowstack
 P = ctypes.c_void_p
 I32, I64, F32, SZ = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 D, L, B = 3, 2, 8
-TENSORS = {"planar": 3, "radial": 3, "affine": 2}
+KINDS = [0, 2]                  # mixed: planar + affine
+N_TABLE = {"planar": 3 * L, "radial": 3 * L, "affine": 2 * L, "mixed": 3 + 2}
 
-HEAD, TAIL = "dim L params x", "B ws wb stream"
+HEADS = dict.fromkeys(("planar", "radial", "affine"), "dim L params x")
+HEADS["mixed"] = "dim L kinds params x"
+TAIL = "B ws wb stream"
 _FWD_LD, _FWD = "z ld z_all", "z z_all"
 _LOSS_LD, _LOSS = "y kind det z ld terms", "y kind z terms"
 _VJP_LD, _VJP = "gz gz_all gld grads dx", "gz gz_all grads dx"
@@ -38,17 +44,31 @@ SIGS = {
     "affine": {"forward": _FWD_LD, "inverse": _FWD_LD, "forward_loss": _LOSS_LD,
                "predict": "lp probs", "score": _SCORE, "vjp": _VJP_LD, "loss_vjp": _LV_DET},
 }
+SIGS["mixed"] = SIGS["planar"]
 ENTRIES = [(fam, e) for fam in SIGS for e in SIGS[fam]]
-assert len(ENTRIES) == 19
+assert len(ENTRIES) == 19 + 6
+
+
+def names(fam, entry):
+    return (HEADS[fam] + " " + SIGS[fam][entry] + " " + TAIL).split()
+
+
+def kinds_of(fam, vals=KINDS):
+    """The `kinds` argument of a family's calls (none unless its head has one)."""
+    return (I32 * len(vals))(*vals) if "kinds" in HEADS[fam] else None
+
 
 CTYPES = {"dim": I32, "L": I32, "kind": I32, "bins": I32, "B": I64, "det": F32, "gscale": F32,
           "wb": SZ}
 GOOD = {"dim": D, "L": L, "B": B, "kind": 0, "bins": 15, "det": 1.0, "gscale": 1.0, "stream": 0}
 
 # name: (overrides, status alone).  "bad" lists (index, value) pairs written
-# into the parameter table (index -1: the last entry, tensors * L - 1);
+# into the parameter table (index -1: the last entry, N_TABLE - 1);
 # "only" restricts a fault to entry points that have that argument.
 FAULTS = {
+    "kinds_null": ({"kinds": None}, -1),
+    "kinds_bad_first": ({"kinds": [3, 2]}, -2),
+    "kinds_bad_last": ({"kinds": [0, -1]}, -2),
     "dim_big": ({"dim": 300}, -3),
     "dim_zero": ({"dim": 0}, -2),
     "layers_zero": ({"L": 0}, -2),
@@ -125,23 +145,32 @@ PAIRS = [
     ("record_mis", "table_null"),         # -6
     ("record_null", "entry_mis_first"),   # -1
     ("record_mis", "lp_null"),
+    ("dim_big", "kinds_null"),            # the shape before kinds: -3
+    ("layers_big", "kinds_bad_first"),
+    ("kinds_null", "batch_neg"),          # kinds directly after the shape: -1 ...
+    ("kinds_bad_last", "batch_neg"),      # ... -2
+    ("kinds_bad_first", "table_null"),    # -2
+    ("kinds_null", "entry_mis_first"),    # -1
+    ("kinds_null", "bins_zero"),          # score: kinds before the scoring arguments: -1
+    ("kinds_bad_last", "record_null"),    # -2
+    ("kinds_bad_first", "x_mis"),
 ]
 
 
-def _applies(fault, names):
+def _applies(fault, args):
     over = FAULTS[fault][0]
-    return all(over["only"] in names if k == "only" else k in names or k == "bad" for k in over)
+    return all(over["only"] in args if k == "only" else k in args or k == "bad" for k in over)
 
 
 def _cases():
     out = []
     for fam, entry in ENTRIES:
-        names = (HEAD + " " + SIGS[fam][entry] + " " + TAIL).split()
+        args = names(fam, entry)
         for f in FAULTS:
-            if _applies(f, names):
+            if _applies(f, args):
                 out.append((fam, entry, (f,), FAULTS[f][1]))
         for a, b in PAIRS:
-            if _applies(a, names) and _applies(b, names):
+            if _applies(a, args) and _applies(b, args):
                 assert FAULTS[a][1] != FAULTS[b][1], (a, b)   # or the pair shows nothing
                 out.append((fam, entry, (a, b), FAULTS[a][1]))
     return out
@@ -152,11 +181,10 @@ IDS = ["%s_%s-%s" % (fam, entry, "+".join(fs)) for fam, entry, fs, _ in CASES]
 
 
 def call(fam, entry, faults):
-    names = (HEAD + " " + SIGS[fam][entry] + " " + TAIL).split()
-    nt = TENSORS[fam]
-    vals = dict(GOOD)
-    vals["wb"] = rowstack.workspace_bytes(fam, D, L, B)
-    table = [4096 + 64 * i for i in range(nt * L)]
+    nt = N_TABLE[fam]
+    vals = dict(GOOD, kinds=KINDS)
+    vals["wb"] = rowstack.workspace_bytes(fam, D, L, B, kinds_of(fam))
+    table = [4096 + 64 * i for i in range(nt)]
     null_table = False
     for f in faults:
         for k, v in FAULTS[f][0].items():
@@ -169,17 +197,18 @@ def call(fam, entry, faults):
                 vals["wb"] += v
             elif k != "only":
                 vals[k] = v
-    vals["params"] = None if null_table else (P * (nt * L))(*table)
+    vals["params"] = None if null_table else (P * nt)(*table)
+    vals["kinds"] = None if vals["kinds"] is None else kinds_of(fam, vals["kinds"])
     args = []
-    for n in names:
+    for n in names(fam, entry):
         v = vals.get(n, 16)                      # any other argument: a fake aligned pointer
-        args.append(v if n == "params" else CTYPES.get(n, P)(v))
+        args.append(v if n in ("params", "kinds") else CTYPES.get(n, P)(v))
     return getattr(_lib.lib(), "cnf_%s_%s" % (fam, entry))(*args)
 
 
 @pytest.mark.parametrize("fam,entry,faults,status", CASES, ids=IDS)
 def test_status_and_precedence(fam, entry, faults, status):
-    assert call(fam, entry, faults) == status
+    assert L == len(KINDS) and call(fam, entry, faults) == status
 
 
 def test_table_covers_every_entry_point_and_fault():
@@ -200,6 +229,14 @@ def test_table_covers_every_entry_point_and_fault():
         assert (("kind_bad", "terms_null") in mine) == ("loss" in entry)
         assert (("bins_zero", "batch_neg") in mine) == (entry == "score")
         assert (("grads_null",) in mine) == ("vjp" in entry)
+        # the kinds checks reach exactly the entry points that take kinds
+        has_kinds = "kinds" in names(fam, entry)
+        assert has_kinds == (fam == "mixed") == any("kinds" in f for fs in mine for f in fs)
+        if has_kinds:
+            assert {("kinds_null",), ("kinds_bad_first",), ("kinds_bad_last",),
+                    ("dim_big", "kinds_null"), ("kinds_null", "batch_neg"),
+                    ("kinds_bad_last", "batch_neg")} <= mine
+            assert (("kinds_null", "bins_zero") in mine) == (entry == "score")
 
 
 @pytest.mark.parametrize("fam,entry", [fe for fe in ENTRIES if "loss" not in fe[1]
@@ -207,9 +244,9 @@ def test_table_covers_every_entry_point_and_fault():
 def test_empty_batch_without_outputs_needs_no_device(fam, entry):
     """B == 0 with null buffers returns OK before any HIP call (the entry
     points that zero something at B == 0 run in tests/test_gpu_rowflow_empty.py)."""
-    names = (HEAD + " " + SIGS[fam][entry] + " " + TAIL).split()
-    nt = TENSORS[fam]
-    vals = dict(GOOD, B=0, wb=0, record=16,
-                params=(P * (nt * L))(*[4096 + 64 * i for i in range(nt * L)]))
-    args = [vals[n] if n == "params" else CTYPES.get(n, P)(vals.get(n, 0)) for n in names]
+    nt = N_TABLE[fam]
+    vals = dict(GOOD, B=0, wb=0, record=16, kinds=kinds_of(fam),
+                params=(P * nt)(*[4096 + 64 * i for i in range(nt)]))
+    args = [vals[n] if n in ("params", "kinds") else CTYPES.get(n, P)(vals.get(n, 0))
+            for n in names(fam, entry)]
     assert getattr(_lib.lib(), "cnf_%s_%s" % (fam, entry))(*args) == 0
