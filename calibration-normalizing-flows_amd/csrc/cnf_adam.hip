@@ -54,7 +54,15 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int64_t f = o0 + i;
     const float pv = p[i];
-    // torch's operation order, each product rounded on its own
+    // torch's operation order.  The _rn intrinsics document it and nothing
+    // more: in this toolchain they are plain * and +, and under HIP's default
+    // contraction the gfx950 code object fuses two of the five multiply-adds
+    // into v_fma_f32 (g + wd * p, and p - step_size * (m / denom)); the lerp's
+    // product and both of v's are rounded on their own.  Measured against
+    // torch.optim.Adam's device steps, this form differs from the single-tensor
+    // path in fewer elements than the fully separate one ("Adam
+    // sweep").  Division and square root are the correctly rounded sequences,
+    // and fp32 subnormals are kept.
     float g = a.g[f];
     if (a.wd != 0.f) g = __fadd_rn(g, __fmul_rn(a.wd, pv));            // grad.add(p, alpha=wd)
     float m = a.m[f];
